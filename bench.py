@@ -32,7 +32,15 @@ the launch-to-launch average, which includes the dependent-launch gap and sits j
 `rocprofv3 --kernel-trace --stats -- python bench.py --streams 1` reports per kernel), the median
 of --kernel-rounds such rounds; the average of one event pair per launch is reported beside it.
 
-Single-GPU:  python bench.py [--steps K --warmup W] [--config C1|C2|C3|C4|mgqp|C5]
+A plain run sets up, pre-warms, runs the W warmup and K timed steps and prints `value` and
+`ms_per_step` with the configuration that produced them.  Everything else described above and
+below — `value_streams1`, the per-step-gather and solver-only runs, the kernel-duration rounds and
+rooflines, the other arithmetic build, C4 on one GPU, the l1-pass histogram, the pipelining and
+certification checks, the CPU baseline and the whole-batch parity check — runs after the timed
+steps with --full only.  --dump-outputs DIR writes the last timed step's x, f and status as
+DIR/<name>.npy (the inputs depend on the arguments alone, so two builds compare output for output).
+
+Single-GPU:  python bench.py [--steps K --warmup W] [--config C1|C2|C3|C4|mgqp|C5] [--full]
 Multi-GPU:   python bench.py --gpus N ...   (starts torch.distributed.run with N ranks itself)
              python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
@@ -143,6 +151,18 @@ def parse(argv=None):
     ap.add_argument("--no-shadow", action="store_true",
                     help="A/B: n > 64 default path's l1 scans in fp64 only (no fp32 copy of CI)")
     ap.add_argument("--no-c4", action="store_true", help="skip the N = 1 line's C4-on-one-GPU record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line can "
+                         "hold: the pipelining check, the serialized and (N > 1) per-step-gather / "
+                         "solver-only runs, kernel-duration rounds and rooflines, the other arithmetic "
+                         "build, C4 on one GPU, the l1-pass histogram, certification counts, the CPU "
+                         "baseline and whole-batch parity (--kernel-*, --cpu-seconds, --no-cpu, "
+                         "--no-c4, --traffic-json, --ops-json apply to these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the results of the last timed step (what the caller of that solve "
+                         "receives: x, f, status per QP in QP order; N > 1: as gathered on rank 0) to "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of "
+                         "the QPs beyond that, its indices in DIR/qp_index.npy)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--ops-json", default=os.path.join(ROOT, "profiles", "op_counts.json"))
     args = ap.parse_args(argv)
@@ -318,6 +338,36 @@ def input_set_count(args, set_bytes):
     return max(3, math.ceil(2 * MALL_BYTES / set_bytes))
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # --dump-outputs: bytes of array data in all
+
+
+def dump_sample(B, n, seed):
+    """QP indices --dump-outputs keeps (sorted), or None for all B: x, f, status and the index
+    itself take 8 (n + 3) bytes per kept QP."""
+    import numpy as np
+
+    keep = (DUMP_BUDGET - 4096) // (8 * (n + 3))
+    if B <= keep:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+
+
+def dump_outputs(path, x, f, status, seed):
+    """x (B, n), f (B,), status (B,) of the last timed step, in QP order, as float64 .npy files."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(len(f), x.shape[1], seed)
+    if idx is not None:
+        x, f, status = x[idx], f[idx], status[idx]
+        np.save(os.path.join(path, "qp_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(path, "qp_index.npy")):
+        os.remove(os.path.join(path, "qp_index.npy"))  # an earlier, sampled dump's
+    np.save(os.path.join(path, "x.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(path, "f.npy"), np.ascontiguousarray(f, dtype=np.float64))
+    np.save(os.path.join(path, "status.npy"), np.asarray(status).astype(np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -471,6 +521,69 @@ def main():
                "note": "untimed solver steps before the W warmup steps (steady-state clocks)"}
     progress(f"{cfg}: timed region, {args.steps} steps after {args.warmup} warmup")
     elapsed = timed(args.steps, args.warmup, S, args.gather if gat else "none")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's x, f, status, or (N > 1 with a
+        # gather) every rank's as rank 0 received them, un-tiled to QP order
+        jl = (args.warmup + args.steps - 1) % S
+
+        def host(x_, f_, s_):
+            x_ = x_.reshape(-1)
+            x_ = qpgpu.from_tiled64(x_, B, (n,)) if args.layout == "tiled64" else x_.reshape(-1, n)[:B]
+            return x_, f_[:B], s_[:B]
+
+        if gat:
+            parts = []
+            for rec in gat.received(jl):
+                a = np.ascontiguousarray(rec.cpu().numpy())
+                parts.append(host(np.ascontiguousarray(a[:, :2 * n]).view(np.float64),
+                                  np.ascontiguousarray(a[:B, 2 * n:2 * n + 2]).view(np.float64).reshape(-1),
+                                  a[:B, 2 * n + 2]))
+            dumped = [np.concatenate(c) for c in zip(*parts)]
+        else:
+            dumped = host(*(t.cpu().numpy() for t in outs[jl]))
+        dump_outputs(args.dump_outputs, *dumped, seed=args.seed)
+
+    def headline(el):
+        par = f"batch-sharded x{world}"
+        if world > 1:
+            par += ((f", {'RCCL' if backend == 'nccl' else backend} gather of (x, f, status) to rank 0 "
+                     + ("once per job (the last step's results)" if args.gather == "final"
+                        else "per step (overlapped)")) if gather else ", no collective")
+        return {
+            "metric": metric_name(cfg, n, p, m, B, world),
+            "value": B * world * args.steps / el,
+            "unit": "QP solves/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "prewarm": prewarm,
+            "warmup": args.warmup,
+            "ms_per_step": el * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": desc, "kind": kind, "n": n, "p": p, "m": m, "batch_per_gpu": B,
+                       "global_batch": B * world, "kernel": kname, "layout": args.layout,
+                       "arithmetic": arithmetic_of(kname) + (" [A/B: fp64-only l1 scans]" if args.no_shadow else ""),
+                       "streams": S, "input_sets": R, "cold_inputs": R > 1 or in_bytes * B >= 2 * MALL_BYTES,
+                       "backend": backend if world > 1 else None, "parallelism": par},
+            "per_gpu_batch": B,
+            "build": qpgpu.build_provenance(),
+        }
+
+    if not args.full:
+        # the plain run: the headline figure alone (the slowest rank's time)
+        if dist:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t[0])
+        if rank == 0:
+            print(json.dumps(headline(elapsed)), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+    # --full from here on
     # the last step of every stream slot, checked against set 0's solve rotated (guards the
     # pipelining and the rotated sets): x, f, status bit for bit
     last = {}
@@ -748,38 +861,14 @@ def main():
     roofline["pipelined"] = {"achieved": pipe_gbs, "frac": pipe_gbs / HBM_PEAK_GBS, "unit": "GB/s",
                              "streams": S, "ms_per_step": elapsed * 1e3 / args.steps,
                              "per_launch_frac": hbm["frac"]}
-    par = f"batch-sharded x{world}"
-    if world > 1:
-        par += ((f", {'RCCL' if backend == 'nccl' else backend} gather of (x, f, status) to rank 0 "
-                 + ("once per job (the last step's results)" if args.gather == "final"
-                    else "per step (overlapped)")) if gather else ", no collective")
-    out = {
-        "metric": metric_name(cfg, n, p, m, B, world),
-        "value": total / elapsed,
-        "unit": "QP solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "prewarm": prewarm,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": desc, "kind": kind, "n": n, "p": p, "m": m, "batch_per_gpu": B,
-                   "global_batch": B * world, "kernel": kname, "layout": args.layout,
-                   "arithmetic": arithmetic_of(kname) + (" [A/B: fp64-only l1 scans]" if args.no_shadow else ""),
-                   "streams": S, "input_sets": R, "cold_inputs": R > 1 or in_bytes * B >= 2 * MALL_BYTES,
-                   "backend": backend if world > 1 else None, "parallelism": par},
-        "per_gpu_batch": B,
+    out = headline(elapsed)
+    out.update({
         "value_streams1": total / elapsed1,
         "roofline": roofline,
         "l1_pass_histogram": hist,
         "status_ok_frac": st_ok,
         "outputs_consistent": consistent,
-        "build": qpgpu.build_provenance(),
-    }
+    })
     if other:
         out["other_arithmetic"] = other
     if cert:

@@ -168,3 +168,27 @@ def test_bench_parity_record_is_the_plain_per_qp_bar():
     st2 = st.copy()
     st2[3] = 1
     assert bench.parity_record(pr, "qp_major", (x, f, st2), (x, f, st), "self")["status_equal"] == 129
+
+
+def test_bench_dump_outputs_files_and_budget(tmp_path):
+    """bench.py --dump-outputs: x, f, status of a step as float64 .npy files in QP order; a batch
+    beyond the 64 MB budget is cut to one fixed sample of QPs (the seed's), indices beside it;
+    a plain run leaves the extra measurements to --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--dump-outputs", str(tmp_path)])
+    assert a.dump_outputs == str(tmp_path) and not a.full and bench.parse(["--full"]).full
+    rng = np.random.default_rng(1)
+    x, f, st = rng.standard_normal((130, 7)), rng.standard_normal(130), np.arange(130, dtype=np.int32) % 3
+    bench.dump_outputs(str(tmp_path), x, f, st, seed=2026)
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("x", "f", "status")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["x"], x) and np.array_equal(got["f"], f) and np.array_equal(got["status"], st)
+    assert not (tmp_path / "qp_index.npy").exists()
+    # C4 on one GPU (1 048 576 QPs of n = 7: 75 MB of results) is sampled, C1 is not
+    assert bench.dump_sample(65536, 7, 2026) is None
+    idx = bench.dump_sample(bench.C4_GLOBAL, 7, 2026)
+    assert np.array_equal(idx, bench.dump_sample(bench.C4_GLOBAL, 7, 2026))
+    assert np.all(np.diff(idx) > 0) and idx[-1] < bench.C4_GLOBAL
+    assert 0.9 * bench.DUMP_BUDGET < len(idx) * 8 * (7 + 3) <= bench.DUMP_BUDGET
