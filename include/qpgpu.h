@@ -173,6 +173,44 @@ int qpgpu_solve_batched_eq(const qpgpu_problem_desc* d,
                            double* x_eq, double* f_eq, int32_t* status_eq,
                            void* stream);
 
+/* Same as qpgpu_solve_batched, plus the dual side of each QP: the Lagrange multipliers and the
+ * size of the final active set.  Device pointers, enqueue only, graph-capturable like it.
+ *
+ * u is the multiplier vector the reference's Goldfarb-Idnani iteration holds when it returns
+ * (its local u[0..iq) with the index array A[0..iq)), written dense, p + m doubles per QP in the
+ * layout of x (QP-major: u + b*(p+m) + j; TILED64: a per-QP block of E = p + m elements):
+ *     u[b][j]      j < p   multiplier of equality j
+ *     u[b][p + i]  i < m   multiplier of inequality i
+ * Every constraint that is not in the final active set is exactly +0.0.  nact[b] (may be NULL) is
+ * the number of active inequalities.  For any status other than QPGPU_QP_OK the whole block is
+ * +0.0 and nact[b] = 0 (that includes QPGPU_QP_NOT_POSITIVE_DEFINITE, where the reference
+ * throws before u exists).  With p + m == 0, u is not touched and may be NULL; otherwise a NULL u
+ * is QPGPU_ERR_INVALID_ARGUMENT.
+ *
+ * Sign convention (the problem statement at the top of this file): at a solution
+ *     G x + g0 = CE u[0:p] + CI u[p:],   u[p:] >= 0,   u[p+i] != 0 only where CI[:,i]^T x + ci0[i] = 0.
+ *
+ * u is whatever the reference's arithmetic holds, like every other output, including one quirk:
+ * when a full step's add_constraint finds the new column dependent, the reference rolls back x
+ * and the INEQUALITIES' multipliers u[p..iq) to their values at the last l1 pass but leaves the
+ * equalities' u[0..p) as the abandoned step updated them.  On well-posed data this path is not
+ * taken (or changes u below its rounding); on adversarially scaled or tied inputs u can then
+ * miss the identities above while x is still the reference's, bit for bit.
+ *
+ * x, f, status and iters are bit-identical to qpgpu_solve_batched with QPGPU_FLAG_EXACT on the
+ * same inputs: the entry always runs the reference's operation order, as if QPGPU_FLAG_EXACT
+ * were set.  This matters for n > 64 or m > 256, whose default tolerance mode (MFMA panel setup,
+ * tree sums, certification and re-solve launch) has no dual form.  QPGPU_FLAG_FAST is
+ * QPGPU_ERR_INVALID_ARGUMENT here (the fast builds have no dual form either);
+ * QPGPU_FLAG_WRITE_FACTOR, both layouts and the QPGPU_FLAG_FORCE_* flags work as in
+ * qpgpu_solve_batched. */
+int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d,
+                             double* G, const double* g0,
+                             const double* CE, const double* ce0,
+                             const double* CI, const double* ci0,
+                             double* x, double* f, int32_t* status, int32_t* iters,
+                             double* u, int32_t* nact, void* stream);
+
 /* Same, with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -338,6 +338,11 @@ struct QpArgs {
   // diagnostic only (NULL in every product call): per-wave s_memtime stamps at phase
   // boundaries, kStampSlots per wave, written by lane 0.  Never feeds an output.
   uint64_t* stamps;
+  // optional (NULL unless qpgpu_solve_batched_dual): the multipliers the reference holds when it
+  // returns, dense (p + m per QP, laid out like x), and the number of active inequalities.  A
+  // non-NULL u selects each family's dual instantiation at the launch site.
+  double* u;
+  int32_t* nact;
 };
 constexpr int kStampSlots = 18;
 // internal QpArgs.flags bit set by the host when CI and ci0 are 16-byte aligned
@@ -357,7 +362,7 @@ constexpr uint32_t kArgShadow = 0x08000000u;
 // writes the plain status back.  Reasons:
 enum : int {
   kUncDependent = 1 << 0,   // add_constraint: |d_iq| <= 1e6 eps R_norm (rank-deficient / near-dependent column)
-  kUncSetup = 1 << 1,       // panel setup: not positive definite, or pivots spread beyond 1e8
+  kUncSetup = 1 << 1,       // panel setup: not positive definite, or pivots spread beyond 1e4
   kUncMaxIter = 1 << 2,     // the step cap fired
   kUncStepTie = 1 << 3,     // t1 and t2 within 1e-9 relative (partial vs full step)
   kUncZz = 1 << 4,          // z.z within [eps/4, 4 eps] of the reference's |z.z| > eps test

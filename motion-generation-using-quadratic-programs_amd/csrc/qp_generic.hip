@@ -60,8 +60,11 @@ struct GenCtl {
 
 enum : int { G_DONE = 0, G_L1 = 1, G_L2 = 2, G_L2A = 3 };
 
-__global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, double* __restrict__ ws) {
-  __shared__ GenCtl c;
+// DUAL (qpgpu_solve_batched_dual): r and u are carried over the whole active set — the equality
+// phase runs the reference's update_r and its u[:iq] update, the loop's start at row 0 — and the
+// multipliers leave through a.u / a.nact; x, f, status and the l1 passes are the same bits.
+template <bool DUAL>
+__device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict__ ws, GenCtl& c) {
   const int tid = threadIdx.x;
   const bool lead = tid == 0;
   const int64_t b = blockIdx.x;
@@ -199,7 +202,7 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, doub
   // depend on the rows below.  For the same reason the equality phase runs none.
   auto update_r = [&](int iq) {
     if (lead)
-      for (int i = iq - 1; i >= p; i--) {
+      for (int i = iq - 1; i >= (DUAL ? 0 : p); i--) {
         const double s = seq_fma_up<kGU>(0.0, i + 1, iq, [&](int j) { return R_(i, j); },
                                          [&](int j) { return rv[j]; });
         rv[i] = (dv[i] - s) / R_(i, i);
@@ -398,11 +401,14 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, doub
       const int iq = c.iq;
       compute_d();
       update_z(iq);
+      if constexpr (DUAL) update_r(iq);  // the reference's: r for the u[:iq] update below
       if (lead) {
         double t2 = 0.0;
         if (fabs(dot(zv, zv)) > kEps) t2 = (-dot(npv, xv) - EL(ce0b, i)) / dot(zv, npv);
         c.t2 = t2;
         uv[iq] = t2;
+        if constexpr (DUAL)
+          for (int k = 0; k < iq; k++) uv[k] -= t2 * rv[k];
         c.f += 0.5 * (t2 * t2) * dot(zv, npv);
         Av[i] = -i - 1;
       }
@@ -535,13 +541,13 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, doub
         c.f = inf;
         c.phase = G_DONE;
       } else if (t2 >= inf) {  // dual step
-        for (int k = p; k < iq; k++) uv[k] -= t * rv[k];
+        for (int k = DUAL ? 0 : p; k < iq; k++) uv[k] -= t * rv[k];
         uv[iq] += t;
         iai[l] = l;
         c.ok = 2;
       } else {  // primal and dual step
         c.f += t * dot(zv, npv) * (0.5 * t + uv[iq]);
-        for (int k = p; k < iq; k++) uv[k] -= t * rv[k];
+        for (int k = DUAL ? 0 : p; k < iq; k++) uv[k] -= t * rv[k];
         uv[iq] += t;
         c.ok = fabs(t - t2) < kEps ? 3 : 4;
       }
@@ -607,9 +613,35 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, doub
     a.status[b] = c.status;
     if (a.iters) a.iters[b] = c.iter;
   }
+  if constexpr (DUAL) {
+    // u dense, like x: equality j's multiplier is u[j] (A[j] = -j-1: equalities never move);
+    // inequality A[k]'s is u[k] (k in [p, iq)), scattered through the workspace's s array so that
+    // the stores are one per thread and slot; every other slot and every non-OK QP +0.0
+    const bool okq = c.status == QPGPU_QP_OK;
+    const int iq = okq ? c.iq : 0;
+    double* ub = a.u + qbase_rt(b, (int64_t)p + m, T);
+    __syncthreads();  // every thread's reads of s are over
+    for (int i = tid; i < m; i += kGenBS) sv[i] = 0.0;
+    __syncthreads();
+    for (int k = p + tid; k < iq; k += kGenBS) sv[Av[k]] = uv[k];
+    __syncthreads();
+    for (int j = tid; j < p; j += kGenBS) EL(ub, j) = (okq && j <= n) ? uv[j] : 0.0;
+    for (int i = tid; i < m; i += kGenBS) EL(ub, (int64_t)p + i) = sv[i];
+    if (lead && a.nact) a.nact[b] = okq ? iq - p : 0;
+  }
 #undef J_
 #undef R_
 #undef EL
+}
+
+__global__ void __launch_bounds__(kGenBS) qp_generic_kernel(const QpArgs a, double* __restrict__ ws) {
+  __shared__ GenCtl c;
+  generic_body<false>(a, ws, c);
+}
+// qpgpu_solve_batched_dual: a kernel of its own, so the one above is the same code as without it
+__global__ void __launch_bounds__(kGenBS) qp_generic_dual_kernel(const QpArgs a, double* __restrict__ ws) {
+  __shared__ GenCtl c;
+  generic_body<true>(a, ws, c);
 }
 
 }  // namespace qpk
@@ -628,6 +660,9 @@ extern "C" const char* qpk_generic_name(int n, int /*p*/, int m) {
 }
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   if (a->batch <= 0) return hipSuccess;
-  hipLaunchKernelGGL(qpk::qp_generic_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
+  if (a->u)
+    hipLaunchKernelGGL(qpk::qp_generic_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
+  else
+    hipLaunchKernelGGL(qpk::qp_generic_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
   return hipGetLastError();
 }

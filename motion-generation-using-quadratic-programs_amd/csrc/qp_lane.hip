@@ -143,9 +143,15 @@ constexpr int kScanDepth = 2;
 // have written.  In the fast build (-ffp-contract=fast) the SAFE body's multiply-adds are
 // contracted too: a fallback wave keeps the reference's divisions and distance(), not its
 // bitwise results (still within 1e-10).
-template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE>
+// DUAL (qpgpu_solve_batched_dual; the exact build's general instantiation only): r and u are
+// carried over the whole active set — the equality phase runs the reference's update_r and its
+// u[:iq] update, the loop's update_r and u update start at row 0 — and the multipliers leave
+// through a.u / a.nact.  t1, the drop choice and the rollback still look at the inequalities
+// only, so x, f, status and the l1 passes are the same bits.
+template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false>
 __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   static_assert(MM <= 64, "bitmask bookkeeping holds m <= 64");
+  static_assert(!DUAL || (!kFast && !EXACT && PX < 0), "the dual mode is the exact build's general instantiation");
   using RI = RIdx<NM>;
   constexpr int STAGE = kStage;
   constexpr bool F = kFast && !SAFE;
@@ -557,7 +563,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     constexpr int LO = decltype(LoC)::value;
 #pragma unroll
     for (int i = NM - 1; i >= 0; i--) {
-      if (i >= LO && i >= p && i < iq) {
+      if (i >= LO && (DUAL || i >= p) && i < iq) {
         double s = 0.0;
 #pragma unroll
         for (int j = i + 1; j < NM; j++)
@@ -810,6 +816,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       }
       compute_d();
       update_z(kZero);
+      if constexpr (DUAL) update_r(kZero);  // the reference's: r for the u[:i] update below
       // (no update_r and no u[:i] update here: r and the equality constraints' multipliers u[0..p)
       // feed nothing — the active-set loop reads u only for the inequalities (t1, the dual step's
       // drop, the rollback) and x, f never use u — so the reference's back-substitution of every
@@ -821,6 +828,11 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
 #pragma unroll
       for (int k = 0; k < NM; k++) xv[k] += t2 * zv[k];
       uv[i < NM + 1 ? i : NM] = t2;
+      if constexpr (DUAL) {
+#pragma unroll
+        for (int k = 0; k < NM; k++)
+          if (k < i) uv[k] -= t2 * rv[k];
+      }
       fval += 0.5 * (t2 * t2) * znp;
       Av[i < NM + 1 ? i : NM] = -i - 1;
       if (!add_constraint(kZero)) {
@@ -1179,7 +1191,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
           if (dual || prim) {
 #pragma unroll
             for (int k = 0; k < NM; k++)
-              if (k >= p && k < iq) uv[k] -= t * rv[k];  // (u[0..p) are never read)
+              if ((DUAL || k >= p) && k < iq) uv[k] -= t * rv[k];  // (u[0..p) are never read)
             lput_lo<IQLO>(uv, iq, lsel_lo<IQLO>(uv, iq) + t);
           }
           bool add_fail = false;
@@ -1243,6 +1255,28 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     if (a.iters) a.iters[b] = iter;
     a.status[b] = status;
   }
+  if constexpr (DUAL) {
+    // u dense, like x: equality j's multiplier is u[j] (A[j] = -j-1: equalities never move),
+    // inequality A[k]'s is u[k] (k in [p, iq)), every other slot and every non-OK QP +0.0.  The
+    // slot of u[k] differs per lane: MM predicated selects per entry, no private-array index.
+    if (live) {
+      const bool okq = status == QPGPU_QP_OK;
+      double* ub = view(a.u, p + m);
+      for (int j = 0; j < p; j++) ub[j * T] = (okq && j <= NM) ? lsel(uv, j) : 0.0;
+      double ud[MM];
+#pragma unroll
+      for (int i = 0; i < MM; i++) ud[i] = 0.0;
+#pragma unroll
+      for (int k = 0; k < NM; k++) {
+        const bool in = okq && k >= p && k < iq;
+        lput_lo<0>(ud, in ? Av[k] : -1, uv[k]);
+      }
+#pragma unroll
+      for (int i = 0; i < MM; i++)
+        if (i < m) ub[(p + i) * T] = ud[i];
+      if (a.nact) a.nact[b] = okq ? iq - p : 0;
+    }
+  }
   lstamp(a, 4);
   return true;
 }
@@ -1268,12 +1302,29 @@ __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
 #ifndef QPGPU_LANE_PART
 #define QPGPU_LANE_PART 0
 #endif
+#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
+// qpgpu_solve_batched_dual: the general instantiation (run-time n, p, m) carrying r and u over the
+// whole active set.  A kernel of its own, so the kernels above are the same code as without it.
+template <int NM, int MM, int T>
+__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_dual_kernel(const QpArgs a) {
+  __shared__ double sbuf[kStage];
+  lane_body<NM, MM, T, false, -1, true, true>(a, sbuf);
+}
+#endif
 template <int NM, int MM, int T>
 static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream);
 template <int NM, int MM, int T>
 static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
   const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
   const dim3 g((unsigned)blocks), blk(64);
+  if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
+#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
+    hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
+    return hipSuccess;
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
 // A/B builds with one instantiation only refuse every other launch with an error: a launch
 // they skipped silently once returned the previous call's f / status / passes through the host
 // entry's reused device buffers, with x = 0 (profiles/r05_s26)

@@ -250,7 +250,7 @@ __global__ void __launch_bounds__(256) qp_panel_setup_kernel(const QpArgs a, dou
     H[1] = 0.5 * f;
     H[2] = shd[0];
     H[3] = c2;
-    H[4] = shd[3] / shd[2];  // pivot spread: the loop marks QPs beyond 1e8 for the EXACT re-solve
+    H[4] = shd[3] / shd[2];  // pivot spread: the loop marks QPs beyond 1e4 for the EXACT re-solve
   }
 }
 

@@ -466,9 +466,14 @@ __device__ __forceinline__ int rpk(int i, int j, int n) {
 // written, and the kernel re-solves the block with the IEEE forms — which also rewrites the
 // m = 0 snapshot (x_eq / f_eq / st_eq) this attempt may have written.  (With -ffp-contract=fast
 // the fallback's multiply-adds are fused too: within 1e-10, not bitwise.)
-template <int S, int NMAX, int MMAX, bool GJR, int OCC, bool F>
+// DUAL (qpgpu_solve_batched_dual; the exact build, reference operation order only): r and u are
+// carried over the whole active set — the equality phase runs the reference's update_r and its
+// u[:iq] update, the loop's update_r and u update start at row 0 — and the multipliers leave
+// through a.u / a.nact; x, f, status and the l1 passes are the same bits.
+template <int S, int NMAX, int MMAX, bool GJR, int OCC, bool F, bool DUAL = false>
 __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ ws) {
   static_assert(!F || (!GJR && S <= 64), "the fast build covers the one-wave LDS variants");
+  static_assert(!DUAL || !F, "the fast build has no dual mode");
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   bool fok = true;  // F: every fast form this lane evaluated so far was in range
   // (one-wave blocks: a ballot is the block-wide OR)
@@ -1731,7 +1736,8 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       compute_d_z(ctl->iq);
       const uint64_t e1 = clk();
       // (no update_r and no u[:iq] update in the equality phase: r and the equality constraints'
-      // multipliers feed nothing, see update_r)
+      // multipliers feed nothing, see update_r — except in the dual mode, which returns them)
+      if constexpr (DUAL) update_r(ctl->iq, 0);
       const uint64_t e2 = clk();
       teq[0] += e1 - e0;
       teq[1] += e2 - e1;
@@ -1742,6 +1748,8 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         if (fabs(zz) > kEps) t2 = wdiv<F>(-npx - c0, znp, fok);
         ctl->t2 = t2;
         uv[iq] = t2;
+        if constexpr (DUAL)
+          for (int k = 0; k < iq; k++) uv[k] -= t2 * rv[k];
         ctl->f += 0.5 * (t2 * t2) * znp;
         if (pre) {
           if (fabs(zz) >= 0.25 * kEps && fabs(zz) <= 4.0 * kEps) ctl->unc |= kUncZz;
@@ -2307,7 +2315,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       tdet[1] += 1;
       tdet[2] += ctl->iq;
     }
-    update_r(ctl->iq, p);
+    update_r(ctl->iq, DUAL ? 0 : p);
     if (QPGPU_WAVE_STAMPS_DETAIL == 1) tdet[0] += clk() - t1c;
     // t1 = min over active inequalities with r > 0 of u/r (first index on ties), l its constraint
     [[maybe_unused]] double t1best = inf;
@@ -2393,7 +2401,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     kind = ctl->qq;
     if (kind >= 2) {
       const double t = ctl->t;
-      for (int k = p + ls; k < ctl->iq; k += S) uv[k] -= t * rv[k];  // (u[0..p) are never read)
+      for (int k = (DUAL ? 0 : p) + ls; k < ctl->iq; k += S) uv[k] -= t * rv[k];  // (u[0..p) are never read)
       grp_sync<S>();
     }
     t0 = clk();
@@ -2510,6 +2518,24 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       if (a.iters) a.iters[b] = ctl->iter;
     }
   }
+  if constexpr (DUAL) {
+    // u dense, like x: equality j's multiplier is u[j] (A[j] = -j-1: equalities never move);
+    // inequality A[k]'s is u[k] (k in [p, iq)), scattered through the s array in LDS so that the
+    // stores are one per lane and slot; every other slot and every non-OK QP +0.0
+    const bool okq = live && ctl->status == QPGPU_QP_OK;
+    const int iq = okq ? ctl->iq : 0;
+    grp_sync<S>();  // every lane's reads of s are over
+    for (int i = ls; i < m; i += S) sv[i] = 0.0;
+    grp_sync<S>();
+    for (int k = p + ls; k < iq; k += S) sv[Av[k]] = uv[k];
+    grp_sync<S>();
+    if (live) {
+      double* ub = a.u + qbase_rt(bb, p + m, T);
+      for (int j = ls; j < p; j += S) EL(ub, j) = (okq && j <= n) ? uv[j] : 0.0;
+      for (int i = ls; i < m; i += S) EL(ub, p + i) = sv[i];
+      if (lead && a.nact) a.nact[b] = okq ? iq - p : 0;
+    }
+  }
 #undef EL
   return true;
 }
@@ -2535,11 +2561,54 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : O
   }
 }
 
+#if !QPGPU_WAVE_FAST
+// qpgpu_solve_batched_dual: a kernel of its own (one per variant, the OCC = 1 layout), so the
+// kernels above are the same code as without it
+template <int S, int NMAX, int MMAX, bool GJR>
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+    qp_wave_dual_kernel(const QpArgs a, double* __restrict__ ws) {
+  wave_body<S, NMAX, MMAX, GJR, 1, false, true>(a, ws);
+}
+template <int S, int NMAX, int MMAX, bool GJR>
+static hipError_t launch_wave_dual(const QpArgs& a, hipStream_t stream, double* ws) {
+  using C = WaveCfg<S, NMAX, MMAX, GJR>;
+  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
+  // the OCC = 1 instantiation's layout: R packed where that one sets up in registers
+  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
+  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
+  if (lds_bytes > 65536) {  // (see launch_wave)
+    static std::mutex mu;
+    static std::map<int, size_t> granted;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& g = granted[dev];
+    if (lds_bytes > g) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_dual_kernel<S, NMAX, MMAX, GJR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+      g = lds_bytes;
+    }
+  }
+  hipLaunchKernelGGL((qp_wave_dual_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
+                     stream, a, ws);
+  return hipGetLastError();
+}
+#endif
+
 // ------------------------------------------------------------------------------------------
 template <int S, int NMAX, int MMAX, bool GJR>
 static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
+  if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
+#if !QPGPU_WAVE_FAST
+    return launch_wave_dual<S, NMAX, MMAX, GJR>(a, stream, ws);
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
   size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR).stride * sizeof(double);
   // Two-QP-per-wave variants: when a block's LDS leaves room for >= 2 waves per SIMD (<= 20 KiB,
   // i.e. >= 8 one-wave blocks per CU) register pressure is the occupancy limit, so launch the

@@ -203,7 +203,8 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
                               const double* CE, const double* ce0, const double* CI,
                               const double* ci0, double* x, double* f, int32_t* status,
                               int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
-                              void* stream, uint32_t internal = 0);
+                              void* stream, uint32_t internal = 0, double* u = nullptr,
+                              int32_t* nact = nullptr);
 
 int qpgpu_solve_batched(const qpgpu_problem_desc* d, double* G, const double* g0,
                         const double* CE, const double* ce0, const double* CI,
@@ -223,11 +224,39 @@ int qpgpu_solve_batched_eq(const qpgpu_problem_desc* d, double* G, const double*
                             status_eq, stream);
 }
 
+// The multipliers too (include/qpgpu.h).  The dual kernels restate the reference's operation
+// order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps it off the
+// tolerance mode (panel setup, tree sums, certification, re-solve), which has no dual form — and
+// QPGPU_FLAG_FAST is refused.  With p + m == 0 there is nothing to return: the plain kernels run.
+int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
+                             const double* CE, const double* ce0, const double* CI,
+                             const double* ci0, double* x, double* f, int32_t* status,
+                             int32_t* iters, double* u, int32_t* nact, void* stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
+  const bool any = (int64_t)d->p + d->m > 0;
+  if (any && !u) return QPGPU_ERR_INVALID_ARGUMENT;
+  qpgpu_problem_desc de = *d;
+  de.flags |= QPGPU_FLAG_EXACT;
+  if (!any) {
+    if (nact && d->batch > 0) {
+      hipError_t e = hipMemsetAsync(nact, 0, (size_t)d->batch * sizeof(int32_t),
+                                    reinterpret_cast<hipStream_t>(stream));
+      if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    }
+    return solve_batched_impl(&de, G, g0, CE, ce0, CI, ci0, x, f, status, iters, nullptr, nullptr,
+                              nullptr, stream);
+  }
+  return solve_batched_impl(&de, G, g0, CE, ce0, CI, ci0, x, f, status, iters, nullptr, nullptr,
+                            nullptr, stream, 0, u, nact);
+}
+
 static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,
                               const double* CE, const double* ce0, const double* CI,
                               const double* ci0, double* x, double* f, int32_t* status,
                               int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
-                              void* stream, uint32_t internal) {
+                              void* stream, uint32_t internal, double* u, int32_t* nact) {
   int rc = validate(d);
   if (rc) return rc;
   if (d->batch == 0) return QPGPU_SUCCESS;
@@ -256,6 +285,8 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
   a.f_eq = f_eq;
   a.st_eq = st_eq;
   a.stamps = g_stamps;
+  a.u = u;
+  a.nact = nact;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int handled = 0;
   hipError_t e = hipSuccess;
@@ -267,6 +298,15 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
   };
   if (((reinterpret_cast<uintptr_t>(CI) | reinterpret_cast<uintptr_t>(ci0)) & 15u) == 0)
     a.flags |= qpk::kArgAligned16;
+  // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
+  // no elements has a NULL data_ptr.  The wave kernels' l1 scan loads element 0 of a clamped
+  // constraint index without a predicate and discards the value (qp_wave.hip, "a lane's two
+  // constraints"), which faulted on NULL: give the kernels readable memory instead — g0, whose
+  // first element of every QP block (or tile) exists in both layouts.
+  if (!a.CE) a.CE = g0;
+  if (!a.ce0) a.ce0 = g0;
+  if (!a.CI) a.CI = g0;
+  if (!a.ci0) a.ci0 = g0;
   auto launch_wave = [&]() -> int {
     if (fast) {
       e = qpk_launch_medium_fast(&a, s, &handled, nullptr);  // LDS variants (n <= 64, m <= 256)
@@ -315,6 +355,8 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
       if (a.x_eq) c.x_eq = a.x_eq + off(b0, n);
       if (a.f_eq) c.f_eq = a.f_eq + b0;
       if (a.st_eq) c.st_eq = a.st_eq + b0;
+      if (a.u) c.u = a.u + off(b0, p + m);
+      if (a.nact) c.nact = a.nact + b0;
       c.stamps = nullptr;
       e = qpk_launch_generic(&c, s, ws);
       if (e != hipSuccess) break;

@@ -59,6 +59,7 @@ LAYOUTS = {None: 0, "qp_major": LAYOUT_QP_MAJOR, "tiled64": LAYOUT_TILED64}
 EXPORTED_SYMBOLS = (
     "qpgpu_solve_batched",
     "qpgpu_solve_batched_eq",
+    "qpgpu_solve_batched_dual",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -99,6 +100,8 @@ def _load():
     lib.qpgpu_solve_batched.restype = ctypes.c_int
     lib.qpgpu_solve_batched_eq.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 14
     lib.qpgpu_solve_batched_eq.restype = ctypes.c_int
+    lib.qpgpu_solve_batched_dual.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13
+    lib.qpgpu_solve_batched_dual.restype = ctypes.c_int
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -385,10 +388,13 @@ class DeviceBatch:
         self.iters = torch.zeros(self.batch, dtype=torch.int32, device=device) if with_iters else None
 
     def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
-              eq_out=None, exact: bool = False, fast: bool = False):
+              eq_out=None, exact: bool = False, fast: bool = False, dual_out=None):
         """Enqueue one batched solve on `stream` (a torch.cuda.Stream, default current).
         eq_out=(x_eq, f_eq, status_eq) tensors also receive the m = 0 answer
-        (qpgpu_solve_batched_eq)."""
+        (qpgpu_solve_batched_eq).  dual_out=(u, nact) tensors receive the multipliers, p + m
+        float64 per QP in this batch's layout, and the int32 active-inequality counts
+        (qpgpu_solve_batched_dual: reference operation order always; either may be None where
+        the C entry takes NULL).  eq_out and dual_out are separate entries: not both."""
         import torch
 
         if stream is None:
@@ -399,6 +405,13 @@ class DeviceBatch:
         vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         args = [ctypes.byref(d), vp(self.G), vp(self.g0), vp(self.CE), vp(self.ce0), vp(self.CI),
                 vp(self.ci0), vp(self.x), vp(self.f), vp(self.status), vp(self.iters)]
+        if dual_out is not None:
+            if eq_out is not None:
+                raise ValueError("eq_out and dual_out are separate entry points: pass one")
+            u, nact = dual_out
+            rc = LIB.qpgpu_solve_batched_dual(*args, vp(u), vp(nact), ctypes.c_void_p(stream.cuda_stream))
+            _check(rc, "qpgpu_solve_batched_dual")
+            return
         if eq_out is None:
             rc = LIB.qpgpu_solve_batched(*args, ctypes.c_void_p(stream.cuda_stream))
         else:
@@ -432,6 +445,32 @@ class DeviceBatch:
         if self.layout == LAYOUT_TILED64:
             x = from_tiled64(x.reshape(-1), self.batch, (self.n,))
         return x, self.f.cpu().numpy(), self.status.cpu().numpy(), it
+
+
+def solve_batched_dual(pr: Problems, family=None, layout=None, max_iter: int = 0,
+                       write_factor: bool = False, device="cuda:0"):
+    """Solve every QP of `pr` on the GPU and return the multipliers too:
+    (x, f, status, iters, u, nact) as numpy, u of shape (B, p + m) in QP-major order whatever
+    the device layout — u[:, :p] the equalities', u[:, p:] the inequalities' (include/qpgpu.h,
+    qpgpu_solve_batched_dual).  Stages `pr` through device tensors; with write_factor=True,
+    pr.G receives each QP's Cholesky factor."""
+    import torch
+
+    db = DeviceBatch(pr, device, layout=layout)
+    B, E = pr.batch, pr.p + pr.m
+    rows = (B + 63) // 64 * 64 if db.layout == LAYOUT_TILED64 else B
+    u = torch.zeros((rows, E), dtype=torch.float64, device=device)
+    nact = torch.zeros(B, dtype=torch.int32, device=device)
+    db.solve(max_iter=max_iter, write_factor=write_factor, family=family, dual_out=(u, nact))
+    torch.cuda.synchronize(db.x.device)
+    x, f, st, it = db.results()
+    uh = u.cpu().numpy()
+    if db.layout == LAYOUT_TILED64:
+        uh = from_tiled64(uh.reshape(-1), B, (E,))
+    if write_factor:
+        Gh = db.G.cpu().numpy()
+        pr.G[...] = from_tiled64(Gh.reshape(-1), B, (pr.n, pr.n)) if db.layout == LAYOUT_TILED64 else Gh
+    return x, f, st, it, uh.reshape(B, E), nact.cpu().numpy()
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):
