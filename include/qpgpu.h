@@ -211,6 +211,42 @@ int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d,
                              double* x, double* f, int32_t* status, int32_t* iters,
                              double* u, int32_t* nact, void* stream);
 
+/* Bound constraints without a dense CI:
+ *     min 1/2 x^T G x + g0^T x   s.t.   CE^T x + ce0 = 0,   lo <= x <= hi.
+ * Device pointers, enqueue only, graph-capturable like qpgpu_solve_batched.  hi and lo are n
+ * doubles per QP in the layout of x (QP-major: hi + b*n + k; TILED64: a per-QP block of E = n).
+ *
+ * The call is DEFINED as the dense problem (n, p, m = 2n) with CI = [-I, +I] and
+ * ci0 = [hi; -lo] — the limits matrix of reference src/mgqp.cpp:1080-1136: inequality k < n is
+ * the upper bound of variable k, inequality n + k its lower bound.  iters, status, f and max_iter
+ * mean what they mean for that dense problem, and d->m must be 2 * d->n (anything else is
+ * QPGPU_ERR_INVALID_ARGUMENT).  hi[k] = +inf or lo[k] = -inf means "no bound on that side"; this
+ * needs no special handling, the dense form with ci0 = +inf behaves the same way.
+ *
+ * x, f, status and iters are bit-identical to qpgpu_solve_batched with QPGPU_FLAG_EXACT on the
+ * materialised problem (and so to the reference) on every QP for which that solve never forms a
+ * non-finite entry of J, z or x: the box kernels keep the one non-zero term of each sum over a
+ * column of CI and skip the products with its zeros, which are +-0 exactly when the other factor
+ * is finite.  On data that overflows, the dense form turns 0 * inf into NaN and the box form does
+ * not; hi = -inf, lo = +inf and NaN bounds are outside the contract for the same reason.
+ *
+ * The entry always runs the reference's operation order, as if QPGPU_FLAG_EXACT were set (the
+ * n > 64 tolerance mode has no box form), and QPGPU_FLAG_FAST is QPGPU_ERR_INVALID_ARGUMENT.
+ * QPGPU_FLAG_WRITE_FACTOR, both layouts and the QPGPU_FLAG_FORCE_* flags work as in
+ * qpgpu_solve_batched (a forced family that does not cover (n, p, 2n) is
+ * QPGPU_ERR_UNSUPPORTED_SHAPE); the default dispatch follows its order for (n, p, 2n).  NULL hi or
+ * lo with batch > 0 is QPGPU_ERR_INVALID_ARGUMENT; CE and ce0 may be NULL when p = 0. */
+int qpgpu_solve_batched_box(const qpgpu_problem_desc* d,
+                            double* G, const double* g0,
+                            const double* CE, const double* ce0,
+                            const double* hi, const double* lo,
+                            double* x, double* f, int32_t* status, int32_t* iters,
+                            void* stream);
+
+/* Name of the kernel a qpgpu_solve_batched_box launch of shape (n, p) with these flags runs
+ * (every box kernel's name contains "box"); "" for a rejected flag combination or n <= 0. */
+const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags);
+
 /* Same, with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -343,6 +343,11 @@ struct QpArgs {
   // non-NULL u selects each family's dual instantiation at the launch site.
   double* u;
   int32_t* nact;
+  // optional (NULL unless qpgpu_solve_batched_box): the bounds lo <= x <= hi, n per QP laid out
+  // like x, standing for CI = [-I, +I], ci0 = [hi; -lo] (m = 2n).  A non-NULL hi selects each
+  // family's box instantiation at the launch site; those kernels never read CI / ci0.
+  const double* hi;
+  const double* lo;
 };
 constexpr int kStampSlots = 18;
 // internal QpArgs.flags bit set by the host when CI and ci0 are 16-byte aligned

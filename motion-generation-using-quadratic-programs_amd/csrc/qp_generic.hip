@@ -63,7 +63,11 @@ enum : int { G_DONE = 0, G_L1 = 1, G_L2 = 2, G_L2A = 3 };
 // DUAL (qpgpu_solve_batched_dual): r and u are carried over the whole active set — the equality
 // phase runs the reference's update_r and its u[:iq] update, the loop's start at row 0 — and the
 // multipliers leave through a.u / a.nact; x, f, status and the l1 passes are the same bits.
-template <bool DUAL>
+// BOX (qpgpu_solve_batched_box): the inequalities are lo <= x <= hi, i.e. CI = [-I, +I] and
+// ci0 = [hi; -lo] never materialised.  Constraint k bounds variable v = k mod n with sign
+// sg = -1 (k < n, upper) or +1 (lower); the reference's sums over a column of CI reduce to their
+// one non-zero term added to the +0.0 the sum starts from.  a.CI / a.ci0 are not read.
+template <bool DUAL, bool BOX = false>
 __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict__ ws, GenCtl& c) {
   const int tid = threadIdx.x;
   const bool lead = tid == 0;
@@ -94,8 +98,18 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
   const double* g0b = a.g0 + qbase_rt(b, n, T);
   const double* CEb = a.CE + qbase_rt(b, (int64_t)n * p, T);
   const double* ce0b = a.ce0 + qbase_rt(b, p, T);
-  const double* CIb = a.CI + qbase_rt(b, (int64_t)n * m, T);
-  const double* ci0b = a.ci0 + qbase_rt(b, m, T);
+  [[maybe_unused]] const double* CIb = BOX ? nullptr : a.CI + qbase_rt(b, (int64_t)n * m, T);
+  [[maybe_unused]] const double* ci0b = BOX ? nullptr : a.ci0 + qbase_rt(b, m, T);
+  [[maybe_unused]] const double* hib = BOX ? a.hi + qbase_rt(b, n, T) : nullptr;
+  [[maybe_unused]] const double* lob = BOX ? a.lo + qbase_rt(b, n, T) : nullptr;
+  // BOX: s[k] = (0.0 + sg x[v]) + b[k], b = [hi; -lo]
+  [[maybe_unused]] auto box_s = [&](int k) {
+    const bool up = k < n;
+    const int v = up ? k : k - n;
+    const double xs = up ? -xv[v] : xv[v];
+    const double bk = up ? EL(hib, v) : -EL(lob, v);
+    return (0.0 + xs) + bk;
+  };
   const double inf = dinf();
   const int64_t nn = (int64_t)n * n;
 
@@ -208,6 +222,21 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
         rv[i] = (dv[i] - s) / R_(i, i);
       }
     __syncthreads();
+  };
+  // BOX: d = J^T np and z.np for np = sg e_v (the loop's; the equality phase keeps the dense forms)
+  [[maybe_unused]] auto compute_d_box = [&](int ip) {
+    const bool up = ip < n;
+    const int v = up ? ip : ip - n;
+    for (int col = tid; col < n; col += kGenBS) {
+      const double jv = J_(v, col);
+      dv[col] = 0.0 + (up ? -jv : jv);
+    }
+    __syncthreads();
+  };
+  [[maybe_unused]] auto znp_box = [&](int ip) {
+    const bool up = ip < n;
+    const double zvv = zv[up ? ip : ip - n];
+    return 0.0 + (up ? -zvv : zvv);
   };
   auto dot = [&](const double* u_, const double* v_) {
     return seq_fma_up<kGU>(0.0, 0, n, [&](int i) { return u_[i]; }, [&](int i) { return v_[i]; });
@@ -451,11 +480,15 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
       }
       for (int i = tid; i < m; i += kGenBS) {
         exc[i] = 1;
-        const double c0 = EL(ci0b, i);
-        double s = seq_fma_up<kGU>(0.0, 0, n, [&](int j) { return EL(CIb, (int64_t)j * m + i); },
-                                   [&](int j) { return xv[j]; });
-        s += c0;
-        sv[i] = s;
+        if constexpr (BOX) {
+          sv[i] = box_s(i);
+        } else {
+          const double c0 = EL(ci0b, i);
+          double s = seq_fma_up<kGU>(0.0, 0, n, [&](int j) { return EL(CIb, (int64_t)j * m + i); },
+                                     [&](int j) { return xv[j]; });
+          s += c0;
+          sv[i] = s;
+        }
       }
       __syncthreads();
       if (lead) {
@@ -498,10 +531,11 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
         }
       }
       __syncthreads();
-      if (c.phase == G_L2A) {
-        const int ip = c.ip;
-        for (int j = tid; j < n; j += kGenBS) npv[j] = EL(CIb, (int64_t)j * m + ip);
-      }
+      if constexpr (!BOX)
+        if (c.phase == G_L2A) {
+          const int ip = c.ip;
+          for (int j = tid; j < n; j += kGenBS) npv[j] = EL(CIb, (int64_t)j * m + ip);
+        }
       __syncthreads();
       continue;
     }
@@ -513,7 +547,10 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
     __syncthreads();
     if (c.phase == G_DONE) break;
     const int iq = c.iq;
-    compute_d();
+    if constexpr (BOX)
+      compute_d_box(c.ip);
+    else
+      compute_d();
     update_z(iq);
     update_r(iq);
     if (lead) {
@@ -526,7 +563,7 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
         }
       double t2;
       if (fabs(dot(zv, zv)) > kEps) {
-        t2 = -sv[c.ip] / dot(zv, npv);
+        t2 = -sv[c.ip] / (BOX ? znp_box(c.ip) : dot(zv, npv));
         if (t2 < 0) t2 = inf;  // Takano Akio patch
       } else {
         t2 = inf;
@@ -546,7 +583,7 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
         iai[l] = l;
         c.ok = 2;
       } else {  // primal and dual step
-        c.f += t * dot(zv, npv) * (0.5 * t + uv[iq]);
+        c.f += t * (BOX ? znp_box(c.ip) : dot(zv, npv)) * (0.5 * t + uv[iq]);
         for (int k = DUAL ? 0 : p; k < iq; k++) uv[k] -= t * rv[k];
         uv[iq] += t;
         c.ok = fabs(t - t2) < kEps ? 3 : 4;
@@ -596,9 +633,13 @@ __device__ __forceinline__ void generic_body(const QpArgs& a, double* __restrict
     delete_constraint(c.l);
     if (lead) {
       const int ip = c.ip;
-      const double s = seq_fma_up<kGU>(0.0, 0, n, [&](int k) { return EL(CIb, (int64_t)k * m + ip); },
-                                       [&](int k) { return xv[k]; });
-      sv[ip] = s + EL(ci0b, ip);
+      if constexpr (BOX) {
+        sv[ip] = box_s(ip);
+      } else {
+        const double s = seq_fma_up<kGU>(0.0, 0, n, [&](int k) { return EL(CIb, (int64_t)k * m + ip); },
+                                         [&](int k) { return xv[k]; });
+        sv[ip] = s + EL(ci0b, ip);
+      }
     }
     __syncthreads();
   }
@@ -643,6 +684,11 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_dual_kernel(const QpArgs a,
   __shared__ GenCtl c;
   generic_body<true>(a, ws, c);
 }
+// qpgpu_solve_batched_box: likewise a kernel of its own
+__global__ void __launch_bounds__(kGenBS) qp_generic_box_kernel(const QpArgs a, double* __restrict__ ws) {
+  __shared__ GenCtl c;
+  generic_body<false, true>(a, ws, c);
+}
 
 }  // namespace qpk
 
@@ -660,7 +706,9 @@ extern "C" const char* qpk_generic_name(int n, int /*p*/, int m) {
 }
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   if (a->batch <= 0) return hipSuccess;
-  if (a->u)
+  if (a->hi)
+    hipLaunchKernelGGL(qpk::qp_generic_box_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
+  else if (a->u)
     hipLaunchKernelGGL(qpk::qp_generic_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
   else
     hipLaunchKernelGGL(qpk::qp_generic_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);

@@ -148,9 +148,17 @@ constexpr int kScanDepth = 2;
 // u[:iq] update, the loop's update_r and u update start at row 0 — and the multipliers leave
 // through a.u / a.nact.  t1, the drop choice and the rollback still look at the inequalities
 // only, so x, f, status and the l1 passes are the same bits.
-template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false>
+// BOX (qpgpu_solve_batched_box; the exact build only): the inequalities are lo <= x <= hi, i.e.
+// CI = [-I, +I] and ci0 = [hi; -lo] never materialised (m = 2n).  The bounds b = [hi; -lo] live in
+// 2 NM registers and so does s, both at compile-time positions: the upper bound of variable v at v,
+// the lower at NM + v (constraint index v and n + v).  The reference's sums over a column of CI
+// reduce to their one non-zero term added to the +0.0 the sum starts from: the l1
+// scan is (0.0 -+ x[v]) + b, d = J^T np is 0.0 -+ J[v][:], z.np is 0.0 -+ z[v].  No CI copy in LDS,
+// no DMA staging, no cache warm-up, no CI / ci0 load of any kind.
+template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false, bool BOX = false>
 __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   static_assert(MM <= 64, "bitmask bookkeeping holds m <= 64");
+  static_assert(!BOX || (!kFast && !DUAL && MM == 2 * NM), "the box mode is the exact build's, m = 2n");
   static_assert(!DUAL || (!kFast && !EXACT && PX < 0), "the dual mode is the exact build's general instantiation");
   using RI = RIdx<NM>;
   constexpr int STAGE = kStage;
@@ -159,7 +167,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // CI / ci0 cache warm-up before the equality phase: only with an equality phase long enough
   // for the loads to land (p > 0 or p unknown).  Measured for p = 0 (no equality phase): the
   // first scan then waits on the same burst either way (profiles/r02_s2, r02_s46).
-  constexpr bool kLanePrefetch = PX != 0;
+  constexpr bool kLanePrefetch = PX != 0 && !BOX;
 
   const int lane = threadIdx.x;
   const int64_t b0 = (int64_t)blockIdx.x * kQpw;
@@ -225,7 +233,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   static_assert(kStageG || QPGPU_LANE_OCC2, "G and g0 staging exceed the stage buffer");
   // CI rows held in LDS through the loop (EXACT QP-major shapes)
   constexpr int kCiRowsFit = (RB / kQpw) / MM;
-  constexpr int kCiRows = (EXACT && T == 1 && MM % 2 == 0) ? (kCiRowsFit < NM ? kCiRowsFit : NM) : 0;
+  constexpr int kCiRows = (!BOX && EXACT && T == 1 && MM % 2 == 0) ? (kCiRowsFit < NM ? kCiRowsFit : NM) : 0;
   // Rows 0..kCiRows-1 of every lane's CI go straight from HBM into that LDS copy by per-lane
   // LDS-DMA while the setup / equality phase computes (kCiDma: p compile-time, CI 16-B aligned),
   // so the first l1 scan finds them on chip instead of re-reading all of CI from the Infinity
@@ -277,6 +285,19 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
                                          16, 0, 0);
   };
   lstamp(a, 0);
+  // BOX: b = [hi; -lo] at the positions above, loaded first so that the setup hides the latency
+  [[maybe_unused]] double bv[BOX ? MM : 1];
+  if constexpr (BOX) {
+    const double* hib = view(const_cast<double*>(a.hi), n);
+    const double* lob = view(const_cast<double*>(a.lo), n);
+#pragma unroll
+    for (int v = 0; v < NM; v++) {
+      const double h = (live && v < n) ? hib[v * T] : 0.0;
+      const double l = (live && v < n) ? lob[v * T] : 0.0;
+      bv[v] = h;
+      bv[NM + v] = -l;
+    }
+  }
 
   // ---------------------------------------------------------------- setup
   bool chol_ok = live;  // idle lanes (past the batch) never touch LDS slots
@@ -757,6 +778,19 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     return s;
   };
   const auto kZero = std::integral_constant<int, 0>{};
+  // BOX: position (see above) of constraint i, and d = 0.0 -+ J[v][:] for the constraint at pos
+  [[maybe_unused]] auto box_pos = [&](int i) -> int { return i < n ? i : NM + (i - n); };
+  [[maybe_unused]] auto compute_d_box = [&](int pos) {
+    const bool up = pos < NM;
+    const int v = up ? pos : pos - NM;
+#pragma unroll
+    for (int c = 0; c < NM; c++) {
+      double jv = opq_l(Jreg[0][c]);
+#pragma unroll
+      for (int k = 1; k < NM; k++) jv = (k == v) ? opq_l(Jreg[k][c]) : jv;
+      dv[c] = 0.0 + (up ? -jv : jv);
+    }
+  };
 
   // ---------------------------------------------------------------- equality phase
   // Fully unrolled: in step i the active-set size iq equals i (every earlier step added a
@@ -909,8 +943,9 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     bool need_scan = true, need_select = true;
     bool active = !done;
     const int max_steps = a.max_steps;
-    const double* CIg = view(const_cast<double*>(a.CI), n * m);
-    const double* ci0g = view(const_cast<double*>(a.ci0), m);
+    // (BOX: none of the CI / ci0 loaders below is ever called; g0 keeps the pointers valid)
+    const double* CIg = view(const_cast<double*>(BOX ? a.g0 : a.CI), n * m);
+    const double* ci0g = view(const_cast<double*>(BOX ? a.g0 : a.ci0), m);
     // element loaders for this lane's CI / ci0 block.  TILED64: raw buffer loads off a
     // wave-uniform descriptor (tile base) + one lane-offset VGPR + element offset in SGPR/imm,
     // so no 64-bit address per element is kept live.
@@ -923,10 +958,10 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       return reinterpret_cast<double*>(((uint64_t)hi << 32) | lo);
     };
     [[maybe_unused]] const auto rsCI = __builtin_amdgcn_make_buffer_rsrc(
-        uniform_ptr(a.CI + b0 * (int64_t)(n * m)), 0,
+        uniform_ptr(BOX ? a.g0 : a.CI + b0 * (int64_t)(n * m)), 0,
         __builtin_amdgcn_readfirstlane(64 * n * m * 8), 0x00020000);
     [[maybe_unused]] const auto rsci0 = __builtin_amdgcn_make_buffer_rsrc(
-        uniform_ptr(a.ci0 + b0 * (int64_t)m), 0, __builtin_amdgcn_readfirstlane(64 * m * 8),
+        uniform_ptr(BOX ? a.g0 : a.ci0 + b0 * (int64_t)m), 0, __builtin_amdgcn_readfirstlane(64 * m * 8),
         0x00020000);
     auto ldCI = [&](int e) -> double {
       if constexpr (T == 64)
@@ -958,7 +993,20 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
 #pragma unroll
             for (int i = 0; i < MM; i++) sv[i] = 0.0;
           }
-          if (do_scan) {
+          if constexpr (BOX) {
+            if (do_scan) {
+              // uppers then lowers: the reference's constraint order for psi
+#pragma unroll
+              for (int v = 0; v < NM; v++)
+                if (v < n) {
+                  sv[v] = (0.0 + -xv[v]) + bv[v];
+                  sv[NM + v] = (0.0 + xv[v]) + bv[NM + v];
+                }
+#pragma unroll
+              for (int q = 0; q < MM; q++)
+                if ((q < NM ? q : q - NM) < n) psi += (sv[q] < 0.0) ? sv[q] : 0.0;
+            }
+          } else if (do_scan) {
             // QP-major rows of an EXACT even-m shape are 16-B aligned when the arrays are
             // (checked on the host: kArgAligned16): load them as dwordx4, half the instructions
             // and half the cache-line lookups per row
@@ -1102,6 +1150,17 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       nloop++;
       // ---- l2: pick the most violated constraint (ss deliberately not reset: reference quirk)
       if (active && need_select) {
+        if constexpr (BOX) {
+#pragma unroll
+          for (int q = 0; q < MM; q++)
+            if ((q < NM ? q : q - NM) < n) {
+              const int i = q < NM ? q : n + (q - NM);
+              const bool elig = !((act >> i) & 1ull) && !((excl >> i) & 1ull);
+              const bool take = sv[q] < ss && elig;
+              ss = take ? sv[q] : ss;
+              ip = take ? i : ip;
+            }
+        } else {  // (body left at its indentation)
 #pragma unroll
         for (int i = 0; i < MM; i++)
           if (i < m) {
@@ -1110,13 +1169,16 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
             ss = take ? sv[i] : ss;
             ip = take ? i : ip;
           }
+        }
         if (ss >= 0.0) {
           active = false;  // optimal
         } else {
+          if constexpr (!BOX) {  // np gather (BOX forms no np in the loop); body left at its indentation
 #pragma unroll
           for (int j = 0; j < NM; j++)
             npv[j] = (j < n) ? ((j < kCiRows && ci_ready) ? ci_lds_at(j * MM + ip) : ldCI(j * m + ip)) : 0.0;
           ci0ip = ldci0(ip);
+          }
           lput_lo<IQLO>(uv, iq, 0.0);
           lput_lo<IQLO>(Av, iq, ip);
         }
@@ -1136,7 +1198,11 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         } else {
           [[maybe_unused]] uint64_t ts0 = 0;
           if constexpr (QPGPU_LANE_STAMPS == 2) ts0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-          compute_d();
+          [[maybe_unused]] const int ipos = BOX ? box_pos(ip) : ip;  // where s[ip] and b[ip] live
+          if constexpr (BOX)
+            compute_d_box(ipos);
+          else
+            compute_d();
           update_z(kLo);
           update_r(kLo);
           if constexpr (QPGPU_LANE_STAMPS == 2) {
@@ -1157,10 +1223,16 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
               l = take ? opq_l(Av[k]) : l;
             }
           const double zz = dot(zv, zv);
-          const double znp = dot(zv, npv);
+          double znp;
+          if constexpr (BOX) {
+            const double zs = lsel(zv, ipos < NM ? ipos : ipos - NM);
+            znp = 0.0 + (ipos < NM ? -zs : zs);
+          } else {
+            znp = dot(zv, npv);
+          }
           double t2;
           if (fabs(zz) > kEps) {
-            t2 = ldiv<F>(-lsel<MM>(sv, ip), znp, fok);
+            t2 = ldiv<F>(-lsel<MM>(sv, ipos), znp, fok);
             if (t2 < 0) t2 = inf;  // Takano Akio patch
           } else {
             t2 = inf;
@@ -1221,11 +1293,16 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
             need_select = true;
           }
           if (part) {  // refresh s[ip] = CI[:,ip]^T x + ci0[ip]
+            if constexpr (BOX) {
+              const double xs = lsel(xv, ipos < NM ? ipos : ipos - NM);
+              lput_lo<0>(sv, ipos, (0.0 + (ipos < NM ? -xs : xs)) + lsel<MM>(bv, ipos));
+            } else {  // (body left at its indentation)
             double s = 0.0;
 #pragma unroll
             for (int j = 0; j < NM; j++)
               if (j < n) s += npv[j] * xv[j];
             lput_lo<0>(sv, ip, s + ci0ip);
+            }
           }
           if (dual || part) need_scan = need_select = false;
         }
@@ -1310,6 +1387,13 @@ __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_dual_kernel(const QpArgs
   __shared__ double sbuf[kStage];
   lane_body<NM, MM, T, false, -1, true, true>(a, sbuf);
 }
+// qpgpu_solve_batched_box: bounds instead of CI.  Kernels of their own: the compile-time p = 0
+// form of the exact shape (EXACT, PX = 0) and the run-time-shape form (any p, n <= NM).
+template <int NM, int MM, int T, bool EXACT, int PX>
+__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_kernel(const QpArgs a) {
+  __shared__ double sbuf[kStage];
+  lane_body<NM, MM, T, EXACT, PX, true, false, true>(a, sbuf);
+}
 #endif
 template <int NM, int MM, int T>
 static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream);
@@ -1317,6 +1401,18 @@ template <int NM, int MM, int T>
 static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
   const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
   const dim3 g((unsigned)blocks), blk(64);
+  if (a.hi) {  // bounds instead of CI: a box instantiation, or an error
+#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
+    if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
+    if (a.n == NM && a.p == 0)
+      hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+    else
+      hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+    return hipSuccess;
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
   if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
 #if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
     hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
@@ -1388,11 +1484,12 @@ struct LaneVariant {
   int nmax, mmax;
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t);
+  const char* box_name;  // qpgpu_solve_batched_box (the exact build)
 };
 
 static const LaneVariant kLaneVariants[] = {
-    {7, 14, kFast ? "qp_lane_fast<N=7,M=14>" : "qp_lane<N=7,M=14>", launch_lane<7, 14>},
-    {8, 16, kFast ? "qp_lane_fast<N=8,M=16>" : "qp_lane<N=8,M=16>", launch_lane<8, 16>},
+    {7, 14, kFast ? "qp_lane_fast<N=7,M=14>" : "qp_lane<N=7,M=14>", launch_lane<7, 14>, "qp_lane_box<N=7,M=14>"},
+    {8, 16, kFast ? "qp_lane_fast<N=8,M=16>" : "qp_lane<N=8,M=16>", launch_lane<8, 16>, "qp_lane_box<N=8,M=16>"},
 };
 
 const LaneVariant* pick_lane(int n, int m) {
@@ -1425,9 +1522,15 @@ extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStrea
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = v->name;
+  if (name) *name = a->hi ? v->box_name : v->name;
   return v->launch(*a, stream);
 }
+#if !QPGPU_LANE_FAST
+extern "C" const char* qpk_lane_box_name(int n, int /*p*/) {
+  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
+  return v ? v->box_name : nullptr;
+}
+#endif
 
 extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int /*p*/, int m) {
   const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, m);

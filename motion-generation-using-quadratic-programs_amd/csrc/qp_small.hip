@@ -72,6 +72,7 @@ struct SmallCfg {
 
 // the kernel, and a second time with the multipliers carried and returned (a kernel of its own,
 // so the first is the same code as without it)
+#define QP_SMALL_BOX false
 #define QP_SMALL_KERNEL qp_small_kernel
 #define QP_SMALL_DUAL false
 #include "qp_small_kernel.inc"
@@ -82,6 +83,15 @@ struct SmallCfg {
 #include "qp_small_kernel.inc"
 #undef QP_SMALL_KERNEL
 #undef QP_SMALL_DUAL
+#undef QP_SMALL_BOX
+// a third time for bound constraints (qpgpu_solve_batched_box)
+#define QP_SMALL_KERNEL qp_small_box_kernel
+#define QP_SMALL_DUAL false
+#define QP_SMALL_BOX true
+#include "qp_small_kernel.inc"
+#undef QP_SMALL_KERNEL
+#undef QP_SMALL_DUAL
+#undef QP_SMALL_BOX
 
 // ------------------------------------------------------------------------------------------
 // launch table
@@ -90,6 +100,11 @@ template <int S, int NM, int MM>
 static hipError_t launch_small(const QpArgs& a, hipStream_t stream) {
   using C = SmallCfg<S, NM, MM>;
   const int64_t blocks = (a.batch + C::QPW - 1) / C::QPW;
+  if (a.hi) {
+    hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                       a);
+    return hipGetLastError();
+  }
   if (a.u) {
     hipLaunchKernelGGL((qp_small_dual_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
                        a);
@@ -104,13 +119,14 @@ struct SmallVariant {
   int nmax, mmax;
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t);
+  const char* box_name;
 };
 
 static const SmallVariant kSmallVariants[] = {
-    {8, 16, "qp_small<S=8,N=8,M=16>", launch_small<8, 8, 16>},
-    {8, 32, "qp_small<S=8,N=8,M=32>", launch_small<8, 8, 32>},
-    {16, 32, "qp_small<S=16,N=16,M=32>", launch_small<16, 16, 32>},
-    {16, 64, "qp_small<S=16,N=16,M=64>", launch_small<16, 16, 64>},
+    {8, 16, "qp_small<S=8,N=8,M=16>", launch_small<8, 8, 16>, "qp_small_box<S=8,N=8,M=16>"},
+    {8, 32, "qp_small<S=8,N=8,M=32>", launch_small<8, 8, 32>, "qp_small_box<S=8,N=8,M=32>"},
+    {16, 32, "qp_small<S=16,N=16,M=32>", launch_small<16, 16, 32>, "qp_small_box<S=16,N=16,M=32>"},
+    {16, 64, "qp_small<S=16,N=16,M=64>", launch_small<16, 16, 64>, "qp_small_box<S=16,N=16,M=64>"},
 };
 
 const SmallVariant* pick_small(int n, int /*p*/, int m) {
@@ -130,11 +146,15 @@ extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream,
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = v->name;
+  if (name) *name = a->hi ? v->box_name : v->name;
   return v->launch(*a, stream);
 }
 
 extern "C" const char* qpk_small_name(int n, int p, int m) {
   const qpk::SmallVariant* v = qpk::pick_small(n, p, m);
   return v ? v->name : nullptr;
+}
+extern "C" const char* qpk_small_box_name(int n, int p) {
+  const qpk::SmallVariant* v = qpk::pick_small(n, p, 2 * n);
+  return v ? v->box_name : nullptr;
 }

@@ -1,15 +1,21 @@
 // qp_small_kernel.inc — the text of the subgroup kernel, included twice by qp_small.hip:
 //   QP_SMALL_KERNEL = qp_small_kernel,      QP_SMALL_DUAL = false   (qpgpu_solve_batched)
 //   QP_SMALL_KERNEL = qp_small_dual_kernel, QP_SMALL_DUAL = true    (qpgpu_solve_batched_dual)
+//   QP_SMALL_KERNEL = qp_small_box_kernel,  QP_SMALL_BOX = true     (qpgpu_solve_batched_box)
 // The body stays inside the __global__ function, as it was before the dual mode existed: moved into
 // a __device__ template that both kernels call, the S = 16 instantiations of the plain kernel
 // allocated one VGPR fewer (421 -> 420, 490 -> 489), i.e. no longer the same code.
 // DUAL (qpgpu_solve_batched_dual): r and u are carried over the whole active set — the equality
 // phase runs the reference's update_r and its u[:iq] update, the loop's start at row 0 — and the
 // multipliers leave through a.u / a.nact; x, f, status and the l1 passes are the same bits.
+// BOX (qpgpu_solve_batched_box): the inequalities are lo <= x <= hi, i.e. CI = [-I, +I] and
+// ci0 = [hi; -lo] never materialised.  A lane keeps the bound of each constraint it owns instead of
+// a column of CI; the reference's sums over a column reduce to their one non-zero term added to the
+// +0.0 the sum starts from (DESIGN §3.6).  a.CI / a.ci0 are not read.
 template <int S, int NM, int MM>
 __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
   constexpr bool DUAL = QP_SMALL_DUAL;
+  constexpr bool BOX = QP_SMALL_BOX;
   using C = SmallCfg<S, NM, MM>;
   constexpr int RS = C::RS;
   constexpr int RPL = C::RPL;
@@ -47,9 +53,21 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
       Pm[i * RS + j] = Gb[(int64_t)e * T];
     }
   }
-  double CIr[CPL][NM];
-  double ci0r[CPL];
-  {
+  double CIr[BOX ? 1 : CPL][BOX ? 1 : NM];
+  double ci0r[CPL];  // BOX: b = [hi; -lo] at this lane's constraints
+  if constexpr (BOX) {
+    const double* hib = a.hi + qbase_rt(b, n, T);
+    const double* lob = a.lo + qbase_rt(b, n, T);
+#pragma unroll
+    for (int q = 0; q < CPL; q++) {
+      const int c = ls + q * S;
+      const bool up = c < n;
+      const int v = up ? c : c - n;
+      const double raw = c < m ? (up ? hib : lob)[(int64_t)v * T] : 0.0;
+      ci0r[q] = up ? raw : -raw;
+    }
+    CIr[0][0] = 0.0;
+  } else {
     const double* CIb = a.CI + qbase_rt(b, n * m, T);
     const double* ci0b = a.ci0 + qbase_rt(b, m, T);
 #pragma unroll
@@ -388,6 +406,33 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
       return s;
     };
 
+    // BOX: constraint c bounds variable v = c mod n; sg a = -a for the upper bounds (c < n)
+    [[maybe_unused]] auto box_sx = [&](int c) -> double {  // 0.0 + sg x[v]
+      const bool up = c < n;
+      const double xs = sel<NM>(xv, up ? c : c - n);
+      return 0.0 + (up ? -xs : xs);
+    };
+    // BOX compute_d: d[i] = 0.0 + sg J[v][i], from the lane that holds row v of J
+    [[maybe_unused]] auto compute_d_box = [&](int c) {
+      const bool up = c < n;
+      const int v = up ? c : c - n;
+      if ((v % S) == ls) {
+        const int qs = v / S;
+#pragma unroll
+        for (int i = 0; i < NM; i++)
+          if (i < n) {
+            double jv = opq(Jr[0][i]);
+#pragma unroll
+            for (int q = 1; q < RPL; q++) jv = (q == qs) ? opq(Jr[q][i]) : jv;
+            db[i] = 0.0 + (up ? -jv : jv);
+          }
+      }
+      sg_sync();
+#pragma unroll
+      for (int i = 0; i < NM; i++) dv[i] = (i < n) ? db[i] : 0.0;
+      sg_sync();
+    };
+
     // ---------------------------------------------------------------- equality phase
     bool done = false;
     for (int i = 0; i < p && !done; i++) {
@@ -450,9 +495,13 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
             const int c = ls + q * S;
             if (c < m) {
               double s = 0.0;
+              if constexpr (BOX) {
+                s = box_sx(c);
+              } else {
 #pragma unroll
-              for (int j = 0; j < NM; j++)
-                if (j < n) s += CIr[q][j] * xv[j];
+                for (int j = 0; j < NM; j++)
+                  if (j < n) s += CIr[q][j] * xv[j];
+              }
               s += ci0r[q];
               sb[c] = s;
             }
@@ -493,6 +542,7 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
               }
             }
           if (ss >= 0.0) break;  // optimal
+          if constexpr (!BOX) {  // np gather (BOX forms no np in the loop); body left at its indentation
           if ((ip % S) == ls) {
             const int qs = ip / S;
 #pragma unroll
@@ -513,6 +563,7 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
             npo[q] = (k < n) ? npb[k] : 0.0;
           }
           sg_sync();
+          }
           put<NM + 1>(uv, iq, 0.0);
           put<NM + 1>(Av, iq, ip);
         }
@@ -521,7 +572,10 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
           status = QPGPU_QP_MAX_ITER;
           break;
         }
-        compute_d();
+        if constexpr (BOX)
+          compute_d_box(ip);
+        else
+          compute_d();
         update_z();
         update_r(DUAL ? 0 : p);
         int l = 0;
@@ -535,7 +589,13 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
             l = take ? opq(Av[k]) : l;
           }
         const double zz = dot(zv, zv);
-        const double znp = dot(zv, npv);
+        double znp;
+        if constexpr (BOX) {
+          const double zs = sel<NM>(zv, ip < n ? ip : ip - n);
+          znp = 0.0 + (ip < n ? -zs : zs);
+        } else {
+          znp = dot(zv, npv);
+        }
         double t2;
         if (fabs(zz) > kEps) {
           t2 = -sb[ip] / znp;
@@ -595,14 +655,18 @@ __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
         if ((ip % S) == ls) {
           const int qs = ip / S;
           double s = 0.0;
+          if constexpr (BOX) {
+            s = box_sx(ip);
+          } else {
 #pragma unroll
-          for (int j = 0; j < NM; j++)
-            if (j < n) {
-              double v = opq(CIr[0][j]);
+            for (int j = 0; j < NM; j++)
+              if (j < n) {
+                double v = opq(CIr[0][j]);
 #pragma unroll
-              for (int q = 1; q < CPL; q++) v = (q == qs) ? opq(CIr[q][j]) : v;
-              s += v * xv[j];
-            }
+                for (int q = 1; q < CPL; q++) v = (q == qs) ? opq(CIr[q][j]) : v;
+                s += v * xv[j];
+              }
+          }
           double c0 = opq(ci0r[0]);
 #pragma unroll
           for (int q = 1; q < CPL; q++) c0 = (q == qs) ? opq(ci0r[q]) : c0;

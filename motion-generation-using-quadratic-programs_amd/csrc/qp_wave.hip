@@ -470,10 +470,18 @@ __device__ __forceinline__ int rpk(int i, int j, int n) {
 // carried over the whole active set — the equality phase runs the reference's update_r and its
 // u[:iq] update, the loop's update_r and u update start at row 0 — and the multipliers leave
 // through a.u / a.nact; x, f, status and the l1 passes are the same bits.
-template <int S, int NMAX, int MMAX, bool GJR, int OCC, bool F, bool DUAL = false>
+// BOX (qpgpu_solve_batched_box; the exact build, reference operation order only): the
+// inequalities are lo <= x <= hi, i.e. CI = [-I, +I] and ci0 = [hi; -lo] never materialised.
+// Constraint k bounds variable v = k mod n with sign sg = -1 (k < n) or +1; the l1 scan is
+// (0.0 + sg x[v]) + b[k], d = J^T np is 0.0 + sg J[v][:] and z.np is 0.0 + sg z[v]: the one
+// non-zero term of the reference's sum added to the +0.0 it starts from.  np itself
+// is never formed in the loop.  a.CI / a.ci0 are not read, and the tolerance mode (`pre`, the
+// shadow scan) is compiled out.
+template <int S, int NMAX, int MMAX, bool GJR, int OCC, bool F, bool DUAL = false, bool BOX = false>
 __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ ws) {
   static_assert(!F || (!GJR && S <= 64), "the fast build covers the one-wave LDS variants");
   static_assert(!DUAL || !F, "the fast build has no dual mode");
+  static_assert(!BOX || (!F && !DUAL), "the box mode is the exact build's, without multipliers");
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   bool fok = true;  // F: every fast form this lane evaluated so far was in range
   // (one-wave blocks: a ballot is the block-wide OR)
@@ -539,16 +547,29 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   const double* g0b = a.g0 + qbase_rt(bb, n, T);
   const double* CEb = a.CE + qbase_rt(bb, n * p, T);
   const double* ce0b = a.ce0 + qbase_rt(bb, p, T);
-  const double* CIb = a.CI + qbase_rt(bb, n * m, T);
-  const double* ci0b = a.ci0 + qbase_rt(bb, m, T);
+  [[maybe_unused]] const double* CIb = BOX ? nullptr : a.CI + qbase_rt(bb, n * m, T);
+  [[maybe_unused]] const double* ci0b = BOX ? nullptr : a.ci0 + qbase_rt(bb, m, T);
+  [[maybe_unused]] const double* hib = BOX ? a.hi + qbase_rt(bb, n, T) : nullptr;
+  [[maybe_unused]] const double* lob = BOX ? a.lo + qbase_rt(bb, n, T) : nullptr;
 #define EL(ptr, e) (ptr)[(int64_t)(e) * T]
+  // BOX: b[k] = hi[k] (k < n) or -lo[k - n], and s[k] = (0.0 + sg x[v]) + b[k]; k in [0, 2n)
+  [[maybe_unused]] auto box_b = [&](int k) -> double {
+    const bool up = k < n;
+    const double raw = EL(up ? hib : lob, up ? k : k - n);
+    return up ? raw : -raw;
+  };
+  [[maybe_unused]] auto box_sx = [&](int k) -> double {
+    const bool up = k < n;
+    const double xs = xv[up ? k : k - n];
+    return 0.0 + (up ? -xs : xs);
+  };
   // J in LDS: row-major.  J in the workspace (GJR): column-major, so that the row-parallel work
   // (Givens sweeps, update_z, building J) reads and writes it coalesced across lanes.
 #define J_(i, j) (GJR ? Jm[(j) * JS + (i)] : Jm[(i) * JS + (j)])
 #define R_(i, j) Rm[kPackedR ? rpk((i), (j), n) : (i) * JS + (j)]
 #define L_(i, j) Lm[(i) * JS + (j)]
   // setup already in the workspace (qp_panel.hip): start from its header
-  const bool pre = GJR && (a.flags & kSetupDone);
+  const bool pre = !BOX && GJR && (a.flags & kSetupDone);
   // certification (tolerance mode only): max |x_i| over the run into ctl->xh (kUncXCancel), an
   // LDS atomic per update (a register for it spilled the 128-VGPR workspace kernel)
   // certification: the scale of one s_i's rounding, max ||CI_i||_1 max ||x||_inf + max |ci0_i|
@@ -882,7 +903,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   constexpr bool kDefer2 = kDefer && (QPGPU_WAVE_TOLLOOP & 8);
   int pend2 = -1;
   [[maybe_unused]] double* const gA = GJR ? Jm + BigWs<NMAX>::OFF_G : nullptr;
-  auto compute_d_z = [&](int iq) {
+  auto compute_d_z = [&](int iq, [[maybe_unused]] int bip = -1) {  // bip: BOX, the loop's ip
     {
       if constexpr (GJR && (QPGPU_WAVE_TOLLOOP & 1) && S == 4 * 64 && NMAX <= S) {
         if (pre && n >= 2 * kTolCh) {  // the same test as add_constraint's defer
@@ -1012,9 +1033,18 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
           return;
         }
       }
+      if (BOX && bip >= 0) {
+        const bool up = bip < n;
+        const int v = up ? bip : bip - n;
+        for (int c = ls; c < n; c += S) {
+          const double jv = J_(v, c);
+          dv[c] = 0.0 + (up ? -jv : jv);
+        }
+      } else {  // (body left at its indentation)
       for (int c = ls; c < n; c += S)
         dv[c] = GJR ? seq_fma_up<KG>(0.0, 0, n, [&](int j) { return J_(j, c); }, [&](int j) { return npv[j]; })
                     : seq_fma_up_lds<QPGPU_WAVE_KUDZ>(0.0, 0, n, [&](int j) { return J_(j, c); }, [&](int j) { return npv[j]; });
+      }
       grp_sync<S>();
       for (int r = ls; r < n; r += S)
         zv[r] = GJR ? seq_fma_up<KG>(0.0, iq, n, [&](int j) { return J_(r, j); }, [&](int j) { return dv[j]; })
@@ -1827,7 +1857,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   // The candidates get their fp64 s_i (the same products and the same j-order sum as the fp64
   // scan: the lanes form the n products, the lead adds them) into sv; the other sv entries keep
   // s~_i.  Otherwise (false) the caller scans in fp64, overwriting sv.
-  constexpr bool kShadow = GJR && QPGPU_WAVE_SHADOW && S == 4 * 64 && NMAX <= S;
+  constexpr bool kShadow = !BOX && GJR && QPGPU_WAVE_SHADOW && S == 4 * 64 && NMAX <= S;
   bool shadow_hit = false;
   [[maybe_unused]] auto shadow_scan = [&]() -> bool {
     constexpr int KS = (MMAX + S - 1) / S;  // constraints per lane
@@ -2043,10 +2073,15 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         const int i0 = ls, i1 = ls + S;
         const bool h0 = i0 < m, h1 = i1 < m;
         const int c0i = h0 ? i0 : 0, c1i = h1 ? i1 : c0i;
-        const double c00 = EL(ci0b, c0i), c01 = EL(ci0b, c1i);
+        const double c00 = BOX ? box_b(c0i) : EL(ci0b, c0i), c01 = BOX ? box_b(c1i) : EL(ci0b, c1i);
         constexpr int SKG = OCC >= 4 ? QPGPU_WAVE_SCANKG4 : QPGPU_WAVE_SCANKG;
         double s0 = 0.0, s1 = 0.0;
         int jb = 0;
+        if constexpr (BOX) {  // (m = 2n >= 2: c0i and c1i are constraints of this QP)
+          s0 = box_sx(c0i);
+          s1 = box_sx(c1i);
+          jb = n;
+        }
         for (; jb + SKG <= n; jb += SKG) {
           double a0[SKG], a1[SKG], xw[SKG];
 #pragma unroll
@@ -2104,8 +2139,8 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
           pre_sb = sb;
           pre_ib = ib;
           const int ig = ib != INT_MAX ? ib : 0;
-          pre_np = EL(CIb, (ls < n ? ls : n - 1) * m + ig);
-          pre_c0 = EL(ci0b, ig);
+          pre_np = BOX ? 0.0 : EL(CIb, (ls < n ? ls : n - 1) * m + ig);
+          pre_c0 = BOX ? box_b(ig) : EL(ci0b, ig);
           from_scan = true;
         }
       } else {
@@ -2121,9 +2156,10 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         }
         if (!shadow_hit) {
           for (int i = ls; i < m; i += S) {
-            const double c0 = EL(ci0b, i);  // issued with the first chunk, added last
-            double s = seq_fma_up<KG>(0.0, 0, n, [&](int j) { return EL(CIb, j * m + i); },
-                                  [&](int j) { return xv[j]; });
+            const double c0 = BOX ? box_b(i) : EL(ci0b, i);  // issued with the first chunk, added last
+            double s = BOX ? box_sx(i)
+                           : seq_fma_up<KG>(0.0, 0, n, [&](int j) { return EL(CIb, j * m + i); },
+                                            [&](int j) { return xv[j]; });
             s += c0;
             sv[i] = s;
             exc[i] = 0;
@@ -2277,12 +2313,12 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         } else {
           uv[ctl->iq] = 0.0;
           Av[ctl->iq] = ip;
-          ctl->ci0ip = (kPreSel && from_scan) ? pre_c0 : EL(ci0b, ip);
+          ctl->ci0ip = (kPreSel && from_scan) ? pre_c0 : (BOX ? box_b(ip) : EL(ci0b, ip));
           ctl->phase = PH_STEP;
         }
       }
       grp_sync<S>();
-      if (ctl->phase == PH_STEP) {
+      if (!BOX && ctl->phase == PH_STEP) {
         const int ip = ctl->ip;
         if (kPreSel && from_scan) {
           if (ls < n) npv[ls] = pre_np;
@@ -2307,7 +2343,10 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     grp_sync<S>();
     if (ctl->phase == PH_DONE) continue;
     uint64_t t0 = clk();
-    compute_d_z(ctl->iq);
+    if constexpr (BOX)
+      compute_d_z(ctl->iq, ctl->ip);
+    else
+      compute_d_z(ctl->iq);
     uint64_t t1c = clk();
     tph[2] += t1c - t0;
     int kind = 0;  // 1 infeasible, 2 dual step, 3 full step, 4 partial step
@@ -2364,6 +2403,11 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       }
       double t2, zz, znp;
       dot2_lead(zz, znp);
+      if constexpr (BOX) {  // z.np = 0.0 + sg z[v] (dot2_lead's np sum is dropped)
+        const int ip = ctl->ip;
+        const double zs = zv[ip < n ? ip : ip - n];
+        znp = 0.0 + (ip < n ? -zs : zs);
+      }
       if (fabs(zz) > kEps) {
         t2 = wdiv<F>(-sv[ctl->ip], znp, fok);
         if (t2 < 0) t2 = inf;  // Takano Akio patch
@@ -2459,8 +2503,9 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       tph[5] += clk() - td;
     }
     if (lead) {
-      const double s = seq_fma_up_lds<8>(0.0, 0, n, [&](int k) { return npv[k]; },
-                                [&](int k) { return xv[k]; });
+      const double s = BOX ? box_sx(ctl->ip)
+                           : seq_fma_up_lds<8>(0.0, 0, n, [&](int k) { return npv[k]; },
+                                               [&](int k) { return xv[k]; });
       sv[ctl->ip] = s + ctl->ci0ip;
       ctl->phase = PH_STEP;
     }
@@ -2595,6 +2640,37 @@ static hipError_t launch_wave_dual(const QpArgs& a, hipStream_t stream, double* 
                      stream, a, ws);
   return hipGetLastError();
 }
+// qpgpu_solve_batched_box: likewise a kernel of its own per variant, the OCC = 1 layout
+template <int S, int NMAX, int MMAX, bool GJR>
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+    qp_wave_box_kernel(const QpArgs a, double* __restrict__ ws) {
+  wave_body<S, NMAX, MMAX, GJR, 1, false, false, true>(a, ws);
+}
+template <int S, int NMAX, int MMAX, bool GJR>
+static hipError_t launch_wave_box(const QpArgs& a, hipStream_t stream, double* ws) {
+  using C = WaveCfg<S, NMAX, MMAX, GJR>;
+  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
+  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
+  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
+  if (lds_bytes > 65536) {  // (see launch_wave)
+    static std::mutex mu;
+    static std::map<int, size_t> granted;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& g = granted[dev];
+    if (lds_bytes > g) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_box_kernel<S, NMAX, MMAX, GJR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+      g = lds_bytes;
+    }
+  }
+  hipLaunchKernelGGL((qp_wave_box_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
+                     stream, a, ws);
+  return hipGetLastError();
+}
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -2602,6 +2678,13 @@ template <int S, int NMAX, int MMAX, bool GJR>
 static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
+  if (a.hi) {  // bounds instead of CI: the box instantiation, or an error
+#if !QPGPU_WAVE_FAST
+    return launch_wave_box<S, NMAX, MMAX, GJR>(a, stream, ws);
+#else
+    return hipErrorInvalidValue;
+#endif
+  }
   if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
 #if !QPGPU_WAVE_FAST
     return launch_wave_dual<S, NMAX, MMAX, GJR>(a, stream, ws);
@@ -2666,6 +2749,7 @@ struct WaveVariant {
   int64_t ws_doubles_per_qp;
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t, double*);
+  const char* box_name;
 };
 
 #if QPGPU_WAVE_FAST
@@ -2673,18 +2757,19 @@ struct WaveVariant {
 #else
 #define QPK_WAVE_VNAME(s) "qp_wave<" s ">"
 #endif
+#define QPK_WAVE_BNAME(s) "qp_wave_box<" s ">"
 static const WaveVariant kWaveVariants[] = {
 #if QPGPU_WAVE_S16
-    {16, 32, 0, QPK_WAVE_VNAME("S=16,N=16,M=32"), launch_wave<16, 16, 32, false>},
+    {16, 32, 0, QPK_WAVE_VNAME("S=16,N=16,M=32"), launch_wave<16, 16, 32, false>, QPK_WAVE_BNAME("S=16,N=16,M=32")},
 #endif
-    {32, 64, 0, QPK_WAVE_VNAME("S=32,N=32,M=64"), launch_wave<32, 32, 64, false>},
-    {32, 128, 0, QPK_WAVE_VNAME("S=32,N=32,M=128"), launch_wave<32, 32, 128, false>},
-    {64, 128, 0, QPK_WAVE_VNAME("S=64,N=64,M=128"), launch_wave<64, 64, 128, false>},
-    {64, 256, 0, QPK_WAVE_VNAME("S=64,N=64,M=256"), launch_wave<64, 64, 256, false>},
+    {32, 64, 0, QPK_WAVE_VNAME("S=32,N=32,M=64"), launch_wave<32, 32, 64, false>, QPK_WAVE_BNAME("S=32,N=32,M=64")},
+    {32, 128, 0, QPK_WAVE_VNAME("S=32,N=32,M=128"), launch_wave<32, 32, 128, false>, QPK_WAVE_BNAME("S=32,N=32,M=128")},
+    {64, 128, 0, QPK_WAVE_VNAME("S=64,N=64,M=128"), launch_wave<64, 64, 128, false>, QPK_WAVE_BNAME("S=64,N=64,M=128")},
+    {64, 256, 0, QPK_WAVE_VNAME("S=64,N=64,M=256"), launch_wave<64, 64, 256, false>, QPK_WAVE_BNAME("S=64,N=64,M=256")},
 #if !QPGPU_WAVE_FAST
     {256, 1024, WaveCfg<256, 256, 1024, true>::WS_DOUBLES,
      "qp_panel<MFMA f64 16x16x4> + qp_wave<S=256,N=256,M=1024,global J/R>",
-     launch_wave<256, 256, 1024, true>},
+     launch_wave<256, 256, 1024, true>, "qp_wave_box<S=256,N=256,M=1024,global J/R>"},
 #endif
 };
 
@@ -2718,6 +2803,10 @@ extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t s
 extern "C" const char* qpk_medium_name(int n, int /*p*/, int m) {
   const qpk::WaveVariant* v = qpk::pick_wave(n, m);
   return v ? v->name : nullptr;
+}
+extern "C" const char* qpk_medium_box_name(int n, int /*p*/) {
+  const qpk::WaveVariant* v = qpk::pick_wave(n, 2 * n);
+  return v ? v->box_name : nullptr;
 }
 extern "C" int qpk_medium_max_n(void) { return 256; }
 extern "C" int qpk_medium_max_m(void) { return 1024; }
@@ -2762,7 +2851,7 @@ extern "C" hipError_t qpk_launch_medium_ws(const qpk::QpArgs* a, hipStream_t str
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = v->name;
+  if (name) *name = a->hi ? v->box_name : v->name;
   if (uses_panel(v, a->flags)) {
     hipError_t e = qpk_launch_panel_setup(a, stream, ws);
     if (e != hipSuccess) return e;

@@ -40,6 +40,9 @@ extern "C" const char* qpk_generic_name(int n, int p, int m);
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws);
 extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream, int* handled,
                                              const char** name);
+extern "C" const char* qpk_lane_box_name(int n, int p);
+extern "C" const char* qpk_small_box_name(int n, int p);
+extern "C" const char* qpk_medium_box_name(int n, int p);
 extern "C" int qpk_medium_max_n(void);
 extern "C" int qpk_medium_max_m(void);
 extern "C" hipError_t qpk_relayout(int64_t batch, int E, const double* src, double* dst,
@@ -204,7 +207,8 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
                               const double* ci0, double* x, double* f, int32_t* status,
                               int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
                               void* stream, uint32_t internal = 0, double* u = nullptr,
-                              int32_t* nact = nullptr);
+                              int32_t* nact = nullptr, const double* hi = nullptr,
+                              const double* lo = nullptr);
 
 int qpgpu_solve_batched(const qpgpu_problem_desc* d, double* G, const double* g0,
                         const double* CE, const double* ce0, const double* CI,
@@ -252,16 +256,57 @@ int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d, double* G, const doubl
                             nullptr, stream, 0, u, nact);
 }
 
+// Bounds instead of a dense CI (include/qpgpu.h).  The box kernels restate the reference's
+// operation order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps
+// it off the tolerance mode, which has no box form — and QPGPU_FLAG_FAST is refused.
+const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags) {
+  if (!flags_valid(flags) || (flags & QPGPU_FLAG_FAST) || n <= 0 || p < 0 || n > INT32_MAX / 2) return "";
+  const int m = 2 * n;
+  const char* s = nullptr;
+  const char* gen = qpk_generic_covers(n, m) ? "qp_generic_box<BS=256,global workspace>" : nullptr;
+  if (flags & QPGPU_FLAG_FORCE_LANE)
+    s = qpk_lane_box_name(n, p);
+  else if (flags & QPGPU_FLAG_FORCE_SUBGROUP)
+    s = qpk_small_box_name(n, p);
+  else if (flags & QPGPU_FLAG_FORCE_WAVE)
+    s = qpk_medium_box_name(n, p);
+  else if (flags & QPGPU_FLAG_FORCE_GENERIC)
+    s = gen;
+  else {  // the plain entry's order for (n, p, 2n)
+    s = qpk_lane_box_name(n, p);
+    if (!s && default_small(n, m)) s = qpk_small_box_name(n, p);
+    if (!s) s = qpk_medium_box_name(n, p);
+    if (!s) s = gen;
+  }
+  return s ? s : "";
+}
+
+int qpgpu_solve_batched_box(const qpgpu_problem_desc* d, double* G, const double* g0,
+                            const double* CE, const double* ce0, const double* hi,
+                            const double* lo, double* x, double* f, int32_t* status,
+                            int32_t* iters, void* stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0 && (!hi || !lo)) return QPGPU_ERR_INVALID_ARGUMENT;
+  qpgpu_problem_desc de = *d;
+  de.flags |= QPGPU_FLAG_EXACT;
+  return solve_batched_impl(&de, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters, nullptr,
+                            nullptr, nullptr, stream, 0, nullptr, nullptr, hi, lo);
+}
+
 static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,
                               const double* CE, const double* ce0, const double* CI,
                               const double* ci0, double* x, double* f, int32_t* status,
                               int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
-                              void* stream, uint32_t internal, double* u, int32_t* nact) {
+                              void* stream, uint32_t internal, double* u, int32_t* nact,
+                              const double* hi, const double* lo) {
   int rc = validate(d);
   if (rc) return rc;
   if (d->batch == 0) return QPGPU_SUCCESS;
   if (!G || !g0 || !x || !f || !status) return QPGPU_ERR_INVALID_ARGUMENT;
-  if ((d->p > 0 && (!CE || !ce0)) || (d->m > 0 && (!CI || !ci0)))
+  if ((d->p > 0 && (!CE || !ce0)) || (!hi && d->m > 0 && (!CI || !ci0)))
     return QPGPU_ERR_INVALID_ARGUMENT;
   qpk::QpArgs a;
   a.n = d->n;
@@ -287,6 +332,8 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
   a.stamps = g_stamps;
   a.u = u;
   a.nact = nact;
+  a.hi = hi;  // non-NULL: the box kernels, which never read CI / ci0 (left at g0 below)
+  a.lo = lo;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int handled = 0;
   hipError_t e = hipSuccess;
@@ -357,6 +404,9 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
       if (a.st_eq) c.st_eq = a.st_eq + b0;
       if (a.u) c.u = a.u + off(b0, p + m);
       if (a.nact) c.nact = a.nact + b0;
+      if (a.hi) c.hi = a.hi + off(b0, n);
+      if (a.lo) c.lo = a.lo + off(b0, n);
+      if (a.hi) c.CI = c.ci0 = c.g0;  // (never read; kept inside an array of this sub-batch)
       c.stamps = nullptr;
       e = qpk_launch_generic(&c, s, ws);
       if (e != hipSuccess) break;

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "qpgpu_solve_batched",
     "qpgpu_solve_batched_eq",
     "qpgpu_solve_batched_dual",
+    "qpgpu_solve_batched_box",
+    "qpgpu_kernel_name_box",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -102,6 +104,10 @@ def _load():
     lib.qpgpu_solve_batched_eq.restype = ctypes.c_int
     lib.qpgpu_solve_batched_dual.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13
     lib.qpgpu_solve_batched_dual.restype = ctypes.c_int
+    lib.qpgpu_solve_batched_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
+    lib.qpgpu_solve_batched_box.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_box.argtypes = [ctypes.c_int32] * 2 + [ctypes.c_uint32]
+    lib.qpgpu_kernel_name_box.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -155,6 +161,12 @@ def kernel_name(n: int, p: int, m: int, fast: bool = False) -> str:
     if fast:
         return LIB.qpgpu_kernel_name_flags(n, p, m, FLAG_FAST).decode()
     return LIB.qpgpu_kernel_name(n, p, m).decode()
+
+
+def kernel_name_box(n: int, p: int, flags: int = 0) -> str:
+    """The kernel a qpgpu_solve_batched_box launch of shape (n, p) with `flags` runs ("" for a
+    rejected flag combination or n <= 0); every box kernel's name contains "box"."""
+    return LIB.qpgpu_kernel_name_box(n, p, flags).decode()
 
 
 # the n > 64 default path's certification (DESIGN §3.4): a QP whose decisions the tolerance mode
@@ -249,6 +261,48 @@ class Problems:
         return (self.G, self.g0, self.CE, self.ce0, self.CI, self.ci0)
 
 
+@dataclass
+class BoxProblems:
+    """A batch of bound-constrained QPs, lo <= x <= hi instead of a dense CI
+    (qpgpu_solve_batched_box): numpy float64, QP-major."""
+
+    n: int
+    p: int
+    G: np.ndarray  # (B, n, n)
+    g0: np.ndarray  # (B, n)
+    CE: np.ndarray  # (B, n, p)
+    ce0: np.ndarray  # (B, p)
+    hi: np.ndarray  # (B, n)
+    lo: np.ndarray  # (B, n)
+
+    @property
+    def batch(self) -> int:
+        return int(self.G.shape[0])
+
+    @property
+    def m(self) -> int:
+        return 2 * self.n
+
+    def slice(self, b0: int, b1: int) -> "BoxProblems":
+        return BoxProblems(self.n, self.p, self.G[b0:b1].copy(), self.g0[b0:b1].copy(),
+                           self.CE[b0:b1].copy(), self.ce0[b0:b1].copy(), self.hi[b0:b1].copy(),
+                           self.lo[b0:b1].copy())
+
+    def arrays(self):
+        return (self.G, self.g0, self.CE, self.ce0, self.hi, self.lo)
+
+    def to_dense(self) -> Problems:
+        """The dense problem the box entry is defined as: CI = [-I, +I], ci0 = [hi; -lo]
+        (inequality k < n the upper bound of variable k, n + k its lower bound)."""
+        B, n = self.batch, self.n
+        eye = np.eye(n)
+        CI = np.broadcast_to(np.concatenate([-eye, eye], axis=1), (B, n, 2 * n)).copy()
+        ci0 = np.concatenate([np.asarray(self.hi, dtype=np.float64).reshape(B, n),
+                              -np.asarray(self.lo, dtype=np.float64).reshape(B, n)], axis=1)
+        return Problems(n, self.p, 2 * n, self.G.copy(), self.g0.copy(), self.CE.copy(),
+                        self.ce0.copy(), np.ascontiguousarray(CI), np.ascontiguousarray(ci0))
+
+
 def to_tiled64(a: np.ndarray) -> np.ndarray:
     """(B, ...) per-QP blocks -> TILED64 flat array of ceil(B/64) tiles (include/qpgpu.h)."""
     B = a.shape[0]
@@ -313,6 +367,11 @@ def objective_term_scale(G, g0, x):
 def algorithmic_bytes_per_qp(n: int, p: int, m: int) -> int:
     """read G, g0, CE, ce0, CI, ci0; write x and f (status excluded)."""
     return 8 * (n * n + n + n * p + p + n * m + m) + 8 * (n + 1)
+
+
+def algorithmic_bytes_per_qp_box(n: int, p: int) -> int:
+    """The same count for the box entry: read G, g0, CE, ce0, hi, lo; write x and f."""
+    return 8 * (n * n + n + n * p + p + 2 * n + n + 1)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -473,6 +532,76 @@ def solve_batched_dual(pr: Problems, family=None, layout=None, max_iter: int = 0
     return x, f, st, it, uh.reshape(B, E), nact.cpu().numpy()
 
 
+class DeviceBoxBatch:
+    """DeviceBatch for bound-constrained QPs (qpgpu_solve_batched_box): hi and lo, n float64 per
+    QP in the layout of x, instead of CI and ci0."""
+
+    def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
+        import torch
+
+        self.n, self.p, self.m, self.batch = bp.n, bp.p, 2 * bp.n, bp.batch
+        self.layout = LAYOUTS[layout]
+        conv = to_tiled64 if self.layout == LAYOUT_TILED64 else (lambda a: a)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(conv(np.asarray(a, dtype=np.float64)))).to(device)
+        self.G, self.g0, self.CE, self.ce0, self.hi, self.lo = (t(a) for a in bp.arrays())
+        rows = (self.batch + 63) // 64 * 64 if self.layout == LAYOUT_TILED64 else self.batch
+        self.x = torch.zeros((rows, self.n), dtype=torch.float64, device=device)
+        self.f = torch.zeros(self.batch, dtype=torch.float64, device=device)
+        self.status = torch.zeros(self.batch, dtype=torch.int32, device=device)
+        self.iters = torch.zeros(self.batch, dtype=torch.int32, device=device) if with_iters else None
+
+    def _args(self, stream, max_iter, flags):
+        d = ProblemDesc(self.n, self.p, self.m, max_iter, self.batch, flags, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        return d, (ctypes.byref(d), vp(self.G), vp(self.g0), vp(self.CE), vp(self.ce0), vp(self.hi),
+                   vp(self.lo), vp(self.x), vp(self.f), vp(self.status), vp(self.iters),
+                   ctypes.c_void_p(stream.cuda_stream))
+
+    def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
+              flags: int = 0):
+        """Enqueue one batched box solve on `stream` (a torch.cuda.Stream, default current);
+        `flags` are OR-ed in as given (tests pass QPGPU_FLAG_FAST to see it refused)."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(self.x.device)
+        _, args = self._args(stream, max_iter,
+                             (FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family] | flags)
+        _check(LIB.qpgpu_solve_batched_box(*args), "qpgpu_solve_batched_box")
+
+    def launcher(self, stream, max_iter: int = 0, family=None):
+        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
+        argument prebuilt (see DeviceBatch.launcher)."""
+        d, args = self._args(stream, max_iter, FAMILY_FLAGS[family])
+        fn = LIB.qpgpu_solve_batched_box
+
+        def launch():
+            rc = fn(*args)
+            if rc != SUCCESS:
+                _check(rc, "qpgpu_solve_batched_box")
+
+        launch._keep = (d, self)
+        return launch
+
+    def results(self):
+        it = None if self.iters is None else self.iters.cpu().numpy()
+        x = self.x.cpu().numpy()
+        if self.layout == LAYOUT_TILED64:
+            x = from_tiled64(x.reshape(-1), self.batch, (self.n,))
+        return x, self.f.cpu().numpy(), self.status.cpu().numpy(), it
+
+
+def solve_batched_box(bp: BoxProblems, family=None, layout=None, max_iter: int = 0, device="cuda:0"):
+    """Solve every QP of `bp` on the GPU through qpgpu_solve_batched_box: (x, f, status, iters)
+    as numpy, x of shape (B, n) whatever the device layout."""
+    import torch
+
+    db = DeviceBoxBatch(bp, device, layout=layout)
+    db.solve(max_iter=max_iter, family=family)
+    torch.cuda.synchronize(db.x.device)
+    return db.results()
+
+
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):
     """Device conversion of one per-QP array between layouts (torch tensors)."""
     import torch
@@ -541,6 +670,14 @@ def make_problems(kind: str, n: int, p: int, m: int, b0: int, b1: int, seed: int
         cat = lambda k: np.concatenate([getattr(q, k) for q in parts])
         return Problems(n, p, m, cat("G"), cat("g0"), cat("CE"), cat("ce0"), cat("CI"), cat("ci0"))
     return _make_range(kind, n, p, m, b0, b1, seed)
+
+
+def make_box_problems(n: int, p: int, b0: int, b1: int, seed: int = 2026) -> BoxProblems:
+    """QPs [b0, b1) of make_problems("box", n, p, 2n, ...) with the bounds as vectors: the same
+    G, g0, CE, ce0, and hi = 1, lo = -1, so to_dense() equals that call bit for bit."""
+    pr = make_problems("box", n, p, 2 * n, b0, b1, seed)
+    B = b1 - b0
+    return BoxProblems(n, p, pr.G, pr.g0, pr.CE, pr.ce0, np.ones((B, n)), -np.ones((B, n)))
 
 
 def _make_range(kind: str, n: int, p: int, m: int, b0: int, b1: int, seed: int) -> Problems:
