@@ -247,6 +247,43 @@ int qpgpu_solve_batched_box(const qpgpu_problem_desc* d,
  * (every box kernel's name contains "box"); "" for a rejected flag combination or n <= 0. */
 const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags);
 
+/* qpgpu_solve_batched_box plus the dual side: the multipliers of the equalities and of the bounds,
+ * and the size of the final active set.  Device pointers, enqueue only, graph-capturable.
+ *
+ * The call is DEFINED as qpgpu_solve_batched_dual on the materialised problem (n, p, m = 2n) with
+ * CI = [-I, +I], ci0 = [hi; -lo], on every QP that meets the finite-data condition of
+ * qpgpu_solve_batched_box (its comment above): x, f, status and iters are the bits of
+ * qpgpu_solve_batched_box, u and nact the bits of qpgpu_solve_batched_dual on that dense problem.
+ * u is dense, p + 2n doubles per QP in the layout of x (QP-major: u + b*(p+2n) + j; TILED64: a
+ * per-QP block of E = p + 2n elements):
+ *     u[b][j]          j < p   multiplier of equality j
+ *     u[b][p + k]      k < n   multiplier of the upper bound of variable k (x[k] <= hi[k])
+ *     u[b][p + n + k]  k < n   multiplier of the lower bound of variable k (x[k] >= lo[k])
+ * Every slot outside the final active set is exactly +0.0; any status other than QPGPU_QP_OK gives
+ * an all-+0.0 block and nact[b] = 0.  nact may be NULL; a NULL u is QPGPU_ERR_INVALID_ARGUMENT
+ * (p + 2n > 0 always).
+ *
+ * Sign convention: that of qpgpu_solve_batched_dual with CI = [-I, +I], i.e. at a solution
+ *     G x + g0 = CE u[0:p] - u[p:p+n] + u[p+n:],   u[p:] >= 0,
+ * and u[p + k] != 0 only where x[k] sits on that bound.  The rollback quirk described at
+ * qpgpu_solve_batched_dual is kept.
+ *
+ * Arguments: the union of the two entries' rules.  d->m must be 2 * d->n, NULL hi or lo with
+ * batch > 0 and QPGPU_FLAG_FAST are QPGPU_ERR_INVALID_ARGUMENT, QPGPU_FLAG_EXACT is implied, CE
+ * and ce0 may be NULL when p = 0.  QPGPU_FLAG_WRITE_FACTOR, both layouts, max_iter, the
+ * QPGPU_FLAG_FORCE_* flags and the default dispatch work as in qpgpu_solve_batched_box.  No kernel
+ * behind this entry reads a CI or ci0, and none is written anywhere. */
+int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d,
+                                 double* G, const double* g0,
+                                 const double* CE, const double* ce0,
+                                 const double* hi, const double* lo,
+                                 double* x, double* f, int32_t* status, int32_t* iters,
+                                 double* u, int32_t* nact, void* stream);
+
+/* Name of the kernel a qpgpu_solve_batched_box_dual launch of shape (n, p) with these flags runs
+ * (every such name contains "box" and "dual"); "" where qpgpu_kernel_name_box returns "". */
+const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags);
+
 /* Same, with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -689,6 +689,12 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_box_kernel(const QpArgs a, 
   __shared__ GenCtl c;
   generic_body<false, true>(a, ws, c);
 }
+// qpgpu_solve_batched_box_dual: bounds and the multipliers (the two modes touch different statements;
+// the constraint index in A is the slot of u that the epilogue scatters to)
+__global__ void __launch_bounds__(kGenBS) qp_generic_box_dual_kernel(const QpArgs a, double* __restrict__ ws) {
+  __shared__ GenCtl c;
+  generic_body<true, true>(a, ws, c);
+}
 
 }  // namespace qpk
 
@@ -706,7 +712,10 @@ extern "C" const char* qpk_generic_name(int n, int /*p*/, int m) {
 }
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   if (a->batch <= 0) return hipSuccess;
-  if (a->hi)
+  if (a->hi && a->u)
+    hipLaunchKernelGGL(qpk::qp_generic_box_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a,
+                       ws);
+  else if (a->hi)
     hipLaunchKernelGGL(qpk::qp_generic_box_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
   else if (a->u)
     hipLaunchKernelGGL(qpk::qp_generic_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);

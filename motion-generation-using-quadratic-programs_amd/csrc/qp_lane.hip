@@ -147,7 +147,8 @@ constexpr int kScanDepth = 2;
 // carried over the whole active set — the equality phase runs the reference's update_r and its
 // u[:iq] update, the loop's update_r and u update start at row 0 — and the multipliers leave
 // through a.u / a.nact.  t1, the drop choice and the rollback still look at the inequalities
-// only, so x, f, status and the l1 passes are the same bits.
+// only, so x, f, status and the l1 passes are the same bits.  With BOX (qpgpu_solve_batched_box_dual)
+// both box forms carry it; with p = 0 the loop is the box kernel's and only the epilogue is added.
 // BOX (qpgpu_solve_batched_box; the exact build only): the inequalities are lo <= x <= hi, i.e.
 // CI = [-I, +I] and ci0 = [hi; -lo] never materialised (m = 2n).  The bounds b = [hi; -lo] live in
 // 2 NM registers and so does s, both at compile-time positions: the upper bound of variable v at v,
@@ -158,8 +159,9 @@ constexpr int kScanDepth = 2;
 template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false, bool BOX = false>
 __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   static_assert(MM <= 64, "bitmask bookkeeping holds m <= 64");
-  static_assert(!BOX || (!kFast && !DUAL && MM == 2 * NM), "the box mode is the exact build's, m = 2n");
-  static_assert(!DUAL || (!kFast && !EXACT && PX < 0), "the dual mode is the exact build's general instantiation");
+  static_assert(!BOX || (!kFast && MM == 2 * NM), "the box mode is the exact build's, m = 2n");
+  static_assert(!DUAL || (!kFast && (BOX || (!EXACT && PX < 0))),
+                "the dual mode is the exact build's general instantiation, or a box form");
   using RI = RIdx<NM>;
   constexpr int STAGE = kStage;
   constexpr bool F = kFast && !SAFE;
@@ -1343,14 +1345,25 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       double ud[MM];
 #pragma unroll
       for (int i = 0; i < MM; i++) ud[i] = 0.0;
+      // (BOX: ud at the positions of s and b, the upper bound of v at v, the lower at NM + v)
 #pragma unroll
       for (int k = 0; k < NM; k++) {
         const bool in = okq && k >= p && k < iq;
-        lput_lo<0>(ud, in ? Av[k] : -1, uv[k]);
+        const int pos = BOX ? box_pos(Av[k]) : Av[k];
+        lput_lo<0>(ud, in ? pos : -1, uv[k]);
       }
+      if constexpr (BOX) {
+#pragma unroll
+        for (int v = 0; v < NM; v++)
+          if (v < n) {
+            ub[(p + v) * T] = ud[v];
+            ub[(p + n + v) * T] = ud[NM + v];
+          }
+      } else {  // (body left at its indentation)
 #pragma unroll
       for (int i = 0; i < MM; i++)
         if (i < m) ub[(p + i) * T] = ud[i];
+      }
       if (a.nact) a.nact[b] = okq ? iq - p : 0;
     }
   }
@@ -1394,6 +1407,13 @@ __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_kernel(const QpArgs 
   __shared__ double sbuf[kStage];
   lane_body<NM, MM, T, EXACT, PX, true, false, true>(a, sbuf);
 }
+// qpgpu_solve_batched_box_dual: the two box forms with the multipliers carried and returned.
+// Kernels of their own again, so the box and dual kernels above are the same code as without them.
+template <int NM, int MM, int T, bool EXACT, int PX>
+__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_dual_kernel(const QpArgs a) {
+  __shared__ double sbuf[kStage];
+  lane_body<NM, MM, T, EXACT, PX, true, true, true>(a, sbuf);
+}
 #endif
 template <int NM, int MM, int T>
 static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream);
@@ -1404,6 +1424,13 @@ static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
   if (a.hi) {  // bounds instead of CI: a box instantiation, or an error
 #if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
     if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
+    if (a.u) {  // ... and the multipliers: a box-dual instantiation
+      if (a.n == NM && a.p == 0)
+        hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+      else
+        hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+      return hipSuccess;
+    }
     if (a.n == NM && a.p == 0)
       hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
     else
@@ -1484,12 +1511,15 @@ struct LaneVariant {
   int nmax, mmax;
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t);
-  const char* box_name;  // qpgpu_solve_batched_box (the exact build)
+  const char* box_name;       // qpgpu_solve_batched_box (the exact build)
+  const char* box_dual_name;  // qpgpu_solve_batched_box_dual (the exact build)
 };
 
 static const LaneVariant kLaneVariants[] = {
-    {7, 14, kFast ? "qp_lane_fast<N=7,M=14>" : "qp_lane<N=7,M=14>", launch_lane<7, 14>, "qp_lane_box<N=7,M=14>"},
-    {8, 16, kFast ? "qp_lane_fast<N=8,M=16>" : "qp_lane<N=8,M=16>", launch_lane<8, 16>, "qp_lane_box<N=8,M=16>"},
+    {7, 14, kFast ? "qp_lane_fast<N=7,M=14>" : "qp_lane<N=7,M=14>", launch_lane<7, 14>, "qp_lane_box<N=7,M=14>",
+     "qp_lane_box_dual<N=7,M=14>"},
+    {8, 16, kFast ? "qp_lane_fast<N=8,M=16>" : "qp_lane<N=8,M=16>", launch_lane<8, 16>, "qp_lane_box<N=8,M=16>",
+     "qp_lane_box_dual<N=8,M=16>"},
 };
 
 const LaneVariant* pick_lane(int n, int m) {
@@ -1522,13 +1552,17 @@ extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStrea
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = a->hi ? v->box_name : v->name;
+  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
   return v->launch(*a, stream);
 }
 #if !QPGPU_LANE_FAST
 extern "C" const char* qpk_lane_box_name(int n, int /*p*/) {
   const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
   return v ? v->box_name : nullptr;
+}
+extern "C" const char* qpk_lane_box_dual_name(int n, int /*p*/) {
+  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
+  return v ? v->box_dual_name : nullptr;
 }
 #endif
 

@@ -91,6 +91,12 @@ struct SmallCfg {
 #include "qp_small_kernel.inc"
 #undef QP_SMALL_KERNEL
 #undef QP_SMALL_DUAL
+// a fourth time for bound constraints with the multipliers (qpgpu_solve_batched_box_dual)
+#define QP_SMALL_KERNEL qp_small_box_dual_kernel
+#define QP_SMALL_DUAL true
+#include "qp_small_kernel.inc"
+#undef QP_SMALL_KERNEL
+#undef QP_SMALL_DUAL
 #undef QP_SMALL_BOX
 
 // ------------------------------------------------------------------------------------------
@@ -100,6 +106,11 @@ template <int S, int NM, int MM>
 static hipError_t launch_small(const QpArgs& a, hipStream_t stream) {
   using C = SmallCfg<S, NM, MM>;
   const int64_t blocks = (a.batch + C::QPW - 1) / C::QPW;
+  if (a.hi && a.u) {
+    hipLaunchKernelGGL((qp_small_box_dual_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
+                       a);
+    return hipGetLastError();
+  }
   if (a.hi) {
     hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
                        a);
@@ -120,13 +131,18 @@ struct SmallVariant {
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t);
   const char* box_name;
+  const char* box_dual_name;
 };
 
 static const SmallVariant kSmallVariants[] = {
-    {8, 16, "qp_small<S=8,N=8,M=16>", launch_small<8, 8, 16>, "qp_small_box<S=8,N=8,M=16>"},
-    {8, 32, "qp_small<S=8,N=8,M=32>", launch_small<8, 8, 32>, "qp_small_box<S=8,N=8,M=32>"},
-    {16, 32, "qp_small<S=16,N=16,M=32>", launch_small<16, 16, 32>, "qp_small_box<S=16,N=16,M=32>"},
-    {16, 64, "qp_small<S=16,N=16,M=64>", launch_small<16, 16, 64>, "qp_small_box<S=16,N=16,M=64>"},
+    {8, 16, "qp_small<S=8,N=8,M=16>", launch_small<8, 8, 16>, "qp_small_box<S=8,N=8,M=16>",
+     "qp_small_box_dual<S=8,N=8,M=16>"},
+    {8, 32, "qp_small<S=8,N=8,M=32>", launch_small<8, 8, 32>, "qp_small_box<S=8,N=8,M=32>",
+     "qp_small_box_dual<S=8,N=8,M=32>"},
+    {16, 32, "qp_small<S=16,N=16,M=32>", launch_small<16, 16, 32>, "qp_small_box<S=16,N=16,M=32>",
+     "qp_small_box_dual<S=16,N=16,M=32>"},
+    {16, 64, "qp_small<S=16,N=16,M=64>", launch_small<16, 16, 64>, "qp_small_box<S=16,N=16,M=64>",
+     "qp_small_box_dual<S=16,N=16,M=64>"},
 };
 
 const SmallVariant* pick_small(int n, int /*p*/, int m) {
@@ -146,7 +162,7 @@ extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream,
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = a->hi ? v->box_name : v->name;
+  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
   return v->launch(*a, stream);
 }
 
@@ -157,4 +173,8 @@ extern "C" const char* qpk_small_name(int n, int p, int m) {
 extern "C" const char* qpk_small_box_name(int n, int p) {
   const qpk::SmallVariant* v = qpk::pick_small(n, p, 2 * n);
   return v ? v->box_name : nullptr;
+}
+extern "C" const char* qpk_small_box_dual_name(int n, int p) {
+  const qpk::SmallVariant* v = qpk::pick_small(n, p, 2 * n);
+  return v ? v->box_dual_name : nullptr;
 }

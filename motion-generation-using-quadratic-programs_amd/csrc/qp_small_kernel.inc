@@ -1,7 +1,8 @@
-// qp_small_kernel.inc — the text of the subgroup kernel, included twice by qp_small.hip:
+// qp_small_kernel.inc — the text of the subgroup kernel, included four times by qp_small.hip:
 //   QP_SMALL_KERNEL = qp_small_kernel,      QP_SMALL_DUAL = false   (qpgpu_solve_batched)
 //   QP_SMALL_KERNEL = qp_small_dual_kernel, QP_SMALL_DUAL = true    (qpgpu_solve_batched_dual)
 //   QP_SMALL_KERNEL = qp_small_box_kernel,  QP_SMALL_BOX = true     (qpgpu_solve_batched_box)
+//   QP_SMALL_KERNEL = qp_small_box_dual_kernel, both true           (qpgpu_solve_batched_box_dual)
 // The body stays inside the __global__ function, as it was before the dual mode existed: moved into
 // a __device__ template that both kernels call, the S = 16 instantiations of the plain kernel
 // allocated one VGPR fewer (421 -> 420, 490 -> 489), i.e. no longer the same code.
@@ -12,6 +13,8 @@
 // ci0 = [hi; -lo] never materialised.  A lane keeps the bound of each constraint it owns instead of
 // a column of CI; the reference's sums over a column reduce to their one non-zero term added to the
 // +0.0 the sum starts from (DESIGN §3.6).  a.CI / a.ci0 are not read.
+// The two modes touch different statements, so both at once is the box kernel carrying r and u: the
+// constraint index in A is the slot of u (upper bounds [p, p + n), lower [p + n, p + 2n)).
 template <int S, int NM, int MM>
 __global__ void __launch_bounds__(64) QP_SMALL_KERNEL(const QpArgs a) {
   constexpr bool DUAL = QP_SMALL_DUAL;

@@ -476,12 +476,13 @@ __device__ __forceinline__ int rpk(int i, int j, int n) {
 // (0.0 + sg x[v]) + b[k], d = J^T np is 0.0 + sg J[v][:] and z.np is 0.0 + sg z[v]: the one
 // non-zero term of the reference's sum added to the +0.0 it starts from.  np itself
 // is never formed in the loop.  a.CI / a.ci0 are not read, and the tolerance mode (`pre`, the
-// shadow scan) is compiled out.
+// shadow scan) is compiled out.  With DUAL as well (qpgpu_solve_batched_box_dual) the two modes
+// touch different statements; the constraint index in A is the slot of u that the epilogue scatters to.
 template <int S, int NMAX, int MMAX, bool GJR, int OCC, bool F, bool DUAL = false, bool BOX = false>
 __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ ws) {
   static_assert(!F || (!GJR && S <= 64), "the fast build covers the one-wave LDS variants");
   static_assert(!DUAL || !F, "the fast build has no dual mode");
-  static_assert(!BOX || (!F && !DUAL), "the box mode is the exact build's, without multipliers");
+  static_assert(!BOX || !F, "the box mode is the exact build's");
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   bool fok = true;  // F: every fast form this lane evaluated so far was in range
   // (one-wave blocks: a ballot is the block-wide OR)
@@ -2671,6 +2672,37 @@ static hipError_t launch_wave_box(const QpArgs& a, hipStream_t stream, double* w
                      stream, a, ws);
   return hipGetLastError();
 }
+// qpgpu_solve_batched_box_dual: bounds and the multipliers, again a kernel of its own per variant
+template <int S, int NMAX, int MMAX, bool GJR>
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+    qp_wave_box_dual_kernel(const QpArgs a, double* __restrict__ ws) {
+  wave_body<S, NMAX, MMAX, GJR, 1, false, true, true>(a, ws);
+}
+template <int S, int NMAX, int MMAX, bool GJR>
+static hipError_t launch_wave_box_dual(const QpArgs& a, hipStream_t stream, double* ws) {
+  using C = WaveCfg<S, NMAX, MMAX, GJR>;
+  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
+  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
+  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
+  if (lds_bytes > 65536) {  // (see launch_wave)
+    static std::mutex mu;
+    static std::map<int, size_t> granted;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& g = granted[dev];
+    if (lds_bytes > g) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+      g = lds_bytes;
+    }
+  }
+  hipLaunchKernelGGL((qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS),
+                     lds_bytes, stream, a, ws);
+  return hipGetLastError();
+}
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -2680,6 +2712,7 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
   if (a.hi) {  // bounds instead of CI: the box instantiation, or an error
 #if !QPGPU_WAVE_FAST
+    if (a.u) return launch_wave_box_dual<S, NMAX, MMAX, GJR>(a, stream, ws);  // ... and the multipliers
     return launch_wave_box<S, NMAX, MMAX, GJR>(a, stream, ws);
 #else
     return hipErrorInvalidValue;
@@ -2750,6 +2783,7 @@ struct WaveVariant {
   const char* name;
   hipError_t (*launch)(const QpArgs&, hipStream_t, double*);
   const char* box_name;
+  const char* box_dual_name;
 };
 
 #if QPGPU_WAVE_FAST
@@ -2757,7 +2791,7 @@ struct WaveVariant {
 #else
 #define QPK_WAVE_VNAME(s) "qp_wave<" s ">"
 #endif
-#define QPK_WAVE_BNAME(s) "qp_wave_box<" s ">"
+#define QPK_WAVE_BNAME(s) "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"
 static const WaveVariant kWaveVariants[] = {
 #if QPGPU_WAVE_S16
     {16, 32, 0, QPK_WAVE_VNAME("S=16,N=16,M=32"), launch_wave<16, 16, 32, false>, QPK_WAVE_BNAME("S=16,N=16,M=32")},
@@ -2769,7 +2803,7 @@ static const WaveVariant kWaveVariants[] = {
 #if !QPGPU_WAVE_FAST
     {256, 1024, WaveCfg<256, 256, 1024, true>::WS_DOUBLES,
      "qp_panel<MFMA f64 16x16x4> + qp_wave<S=256,N=256,M=1024,global J/R>",
-     launch_wave<256, 256, 1024, true>, "qp_wave_box<S=256,N=256,M=1024,global J/R>"},
+     launch_wave<256, 256, 1024, true>, QPK_WAVE_BNAME("S=256,N=256,M=1024,global J/R")},
 #endif
 };
 
@@ -2807,6 +2841,10 @@ extern "C" const char* qpk_medium_name(int n, int /*p*/, int m) {
 extern "C" const char* qpk_medium_box_name(int n, int /*p*/) {
   const qpk::WaveVariant* v = qpk::pick_wave(n, 2 * n);
   return v ? v->box_name : nullptr;
+}
+extern "C" const char* qpk_medium_box_dual_name(int n, int /*p*/) {
+  const qpk::WaveVariant* v = qpk::pick_wave(n, 2 * n);
+  return v ? v->box_dual_name : nullptr;
 }
 extern "C" int qpk_medium_max_n(void) { return 256; }
 extern "C" int qpk_medium_max_m(void) { return 1024; }
@@ -2851,7 +2889,7 @@ extern "C" hipError_t qpk_launch_medium_ws(const qpk::QpArgs* a, hipStream_t str
     return hipSuccess;
   }
   *handled = 1;
-  if (name) *name = a->hi ? v->box_name : v->name;
+  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
   if (uses_panel(v, a->flags)) {
     hipError_t e = qpk_launch_panel_setup(a, stream, ws);
     if (e != hipSuccess) return e;

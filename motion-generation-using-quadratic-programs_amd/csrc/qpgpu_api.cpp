@@ -43,6 +43,9 @@ extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t s
 extern "C" const char* qpk_lane_box_name(int n, int p);
 extern "C" const char* qpk_small_box_name(int n, int p);
 extern "C" const char* qpk_medium_box_name(int n, int p);
+extern "C" const char* qpk_lane_box_dual_name(int n, int p);
+extern "C" const char* qpk_small_box_dual_name(int n, int p);
+extern "C" const char* qpk_medium_box_dual_name(int n, int p);
 extern "C" int qpk_medium_max_n(void);
 extern "C" int qpk_medium_max_m(void);
 extern "C" hipError_t qpk_relayout(int64_t batch, int E, const double* src, double* dst,
@@ -259,26 +262,39 @@ int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d, double* G, const doubl
 // Bounds instead of a dense CI (include/qpgpu.h).  The box kernels restate the reference's
 // operation order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps
 // it off the tolerance mode, which has no box form — and QPGPU_FLAG_FAST is refused.
-const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags) {
+// (dual: the names of qpgpu_solve_batched_box_dual's kernels, same conditions and order)
+static const char* box_kernel_name(int32_t n, int32_t p, uint32_t flags, bool dual) {
   if (!flags_valid(flags) || (flags & QPGPU_FLAG_FAST) || n <= 0 || p < 0 || n > INT32_MAX / 2) return "";
   const int m = 2 * n;
   const char* s = nullptr;
-  const char* gen = qpk_generic_covers(n, m) ? "qp_generic_box<BS=256,global workspace>" : nullptr;
+  const char* gen = !qpk_generic_covers(n, m) ? nullptr
+                    : dual                    ? "qp_generic_box_dual<BS=256,global workspace>"
+                                              : "qp_generic_box<BS=256,global workspace>";
+  const auto lane = dual ? qpk_lane_box_dual_name : qpk_lane_box_name;
+  const auto small = dual ? qpk_small_box_dual_name : qpk_small_box_name;
+  const auto medium = dual ? qpk_medium_box_dual_name : qpk_medium_box_name;
   if (flags & QPGPU_FLAG_FORCE_LANE)
-    s = qpk_lane_box_name(n, p);
+    s = lane(n, p);
   else if (flags & QPGPU_FLAG_FORCE_SUBGROUP)
-    s = qpk_small_box_name(n, p);
+    s = small(n, p);
   else if (flags & QPGPU_FLAG_FORCE_WAVE)
-    s = qpk_medium_box_name(n, p);
+    s = medium(n, p);
   else if (flags & QPGPU_FLAG_FORCE_GENERIC)
     s = gen;
   else {  // the plain entry's order for (n, p, 2n)
-    s = qpk_lane_box_name(n, p);
-    if (!s && default_small(n, m)) s = qpk_small_box_name(n, p);
-    if (!s) s = qpk_medium_box_name(n, p);
+    s = lane(n, p);
+    if (!s && default_small(n, m)) s = small(n, p);
+    if (!s) s = medium(n, p);
     if (!s) s = gen;
   }
   return s ? s : "";
+}
+
+const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags) {
+  return box_kernel_name(n, p, flags, false);
+}
+const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags) {
+  return box_kernel_name(n, p, flags, true);
 }
 
 int qpgpu_solve_batched_box(const qpgpu_problem_desc* d, double* G, const double* g0,
@@ -294,6 +310,24 @@ int qpgpu_solve_batched_box(const qpgpu_problem_desc* d, double* G, const double
   de.flags |= QPGPU_FLAG_EXACT;
   return solve_batched_impl(&de, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters, nullptr,
                             nullptr, nullptr, stream, 0, nullptr, nullptr, hi, lo);
+}
+
+// Bounds and the multipliers (include/qpgpu.h): the union of the two entries' rules above.  With
+// hi and u both set every family launches its box-dual kernel; no CI is written anywhere.
+int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
+                                 const double* CE, const double* ce0, const double* hi,
+                                 const double* lo, double* x, double* f, int32_t* status,
+                                 int32_t* iters, double* u, int32_t* nact, void* stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0 && (!hi || !lo)) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (!u) return QPGPU_ERR_INVALID_ARGUMENT;  // p + 2n > 0 always
+  qpgpu_problem_desc de = *d;
+  de.flags |= QPGPU_FLAG_EXACT;
+  return solve_batched_impl(&de, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters, nullptr,
+                            nullptr, nullptr, stream, 0, u, nact, hi, lo);
 }
 
 static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,

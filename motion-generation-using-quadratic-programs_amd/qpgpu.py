@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "qpgpu_solve_batched_dual",
     "qpgpu_solve_batched_box",
     "qpgpu_kernel_name_box",
+    "qpgpu_solve_batched_box_dual",
+    "qpgpu_kernel_name_box_dual",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -108,6 +110,10 @@ def _load():
     lib.qpgpu_solve_batched_box.restype = ctypes.c_int
     lib.qpgpu_kernel_name_box.argtypes = [ctypes.c_int32] * 2 + [ctypes.c_uint32]
     lib.qpgpu_kernel_name_box.restype = ctypes.c_char_p
+    lib.qpgpu_solve_batched_box_dual.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13
+    lib.qpgpu_solve_batched_box_dual.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_box_dual.argtypes = [ctypes.c_int32] * 2 + [ctypes.c_uint32]
+    lib.qpgpu_kernel_name_box_dual.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -167,6 +173,12 @@ def kernel_name_box(n: int, p: int, flags: int = 0) -> str:
     """The kernel a qpgpu_solve_batched_box launch of shape (n, p) with `flags` runs ("" for a
     rejected flag combination or n <= 0); every box kernel's name contains "box"."""
     return LIB.qpgpu_kernel_name_box(n, p, flags).decode()
+
+
+def kernel_name_box_dual(n: int, p: int, flags: int = 0) -> str:
+    """The kernel a qpgpu_solve_batched_box_dual launch of shape (n, p) with `flags` runs ("" where
+    kernel_name_box is ""); every such name contains "box" and "dual"."""
+    return LIB.qpgpu_kernel_name_box_dual(n, p, flags).decode()
 
 
 # the n > 64 default path's certification (DESIGN §3.4): a QP whose decisions the tolerance mode
@@ -558,15 +570,24 @@ class DeviceBoxBatch:
                    ctypes.c_void_p(stream.cuda_stream))
 
     def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
-              flags: int = 0):
+              flags: int = 0, dual_out=None):
         """Enqueue one batched box solve on `stream` (a torch.cuda.Stream, default current);
-        `flags` are OR-ed in as given (tests pass QPGPU_FLAG_FAST to see it refused)."""
+        `flags` are OR-ed in as given (tests pass QPGPU_FLAG_FAST to see it refused).
+        dual_out=(u, nact) tensors receive the multipliers, p + 2n float64 per QP in the layout of
+        x, and the active-set sizes, int32 (qpgpu_solve_batched_box_dual; either may be None where
+        the C entry takes NULL)."""
         import torch
 
         if stream is None:
             stream = torch.cuda.current_stream(self.x.device)
         _, args = self._args(stream, max_iter,
                              (FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family] | flags)
+        if dual_out is not None:
+            u, nact = dual_out
+            vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            rc = LIB.qpgpu_solve_batched_box_dual(*args[:-1], vp(u), vp(nact), args[-1])
+            _check(rc, "qpgpu_solve_batched_box_dual")
+            return
         _check(LIB.qpgpu_solve_batched_box(*args), "qpgpu_solve_batched_box")
 
     def launcher(self, stream, max_iter: int = 0, family=None):
@@ -600,6 +621,31 @@ def solve_batched_box(bp: BoxProblems, family=None, layout=None, max_iter: int =
     db.solve(max_iter=max_iter, family=family)
     torch.cuda.synchronize(db.x.device)
     return db.results()
+
+
+def solve_batched_box_dual(bp: BoxProblems, family=None, layout=None, max_iter: int = 0,
+                           write_factor: bool = False, device="cuda:0"):
+    """Solve every QP of `bp` on the GPU through qpgpu_solve_batched_box_dual:
+    (x, f, status, iters, u, nact) as numpy, u of shape (B, p + 2n) in QP-major order whatever the
+    device layout — u[:, :p] the equalities', u[:, p:p+n] the upper bounds', u[:, p+n:] the lower
+    bounds' (include/qpgpu.h).  With write_factor=True, bp.G receives each QP's Cholesky factor."""
+    import torch
+
+    db = DeviceBoxBatch(bp, device, layout=layout)
+    B, E = bp.batch, bp.p + 2 * bp.n
+    rows = (B + 63) // 64 * 64 if db.layout == LAYOUT_TILED64 else B
+    u = torch.zeros((rows, E), dtype=torch.float64, device=device)
+    nact = torch.zeros(B, dtype=torch.int32, device=device)
+    db.solve(max_iter=max_iter, write_factor=write_factor, family=family, dual_out=(u, nact))
+    torch.cuda.synchronize(db.x.device)
+    x, f, st, it = db.results()
+    uh = u.cpu().numpy()
+    if db.layout == LAYOUT_TILED64:
+        uh = from_tiled64(uh.reshape(-1), B, (E,))
+    if write_factor:
+        Gh = db.G.cpu().numpy()
+        bp.G[...] = from_tiled64(Gh.reshape(-1), B, (bp.n, bp.n)) if db.layout == LAYOUT_TILED64 else Gh
+    return x, f, st, it, uh.reshape(B, E), nact.cpu().numpy()
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):
