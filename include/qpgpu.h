@@ -38,6 +38,25 @@
  *     of QP b lives at  X + (b / 64) * 64 * E + e * 64 + (b % 64).
  *     Arrays hold ceil(batch/64) whole tiles; f, status, iters stay one value per QP.
  * qpgpu_relayout() converts one array between the two layouts on the device.
+ *
+ * Where the arrays may lie (every device-pointer entry below):
+ *   - Natural alignment is sufficient: 8 bytes for the float64 arrays, 4 for the int32 ones.  No
+ *     entry needs more, and results do not depend on the alignment: every output is the same bits
+ *     wherever the arrays lie.
+ *   - 16-byte alignment of the float64 INPUT arrays enables the staged paths of the lane kernels
+ *     (n <= 8, m <= 16), in two independent groups: G, g0 and, with p > 0, CE and ce0 (their copy
+ *     into on-chip memory by 16-byte transfers); CI and ci0 (the on-chip copy of CI and 16-byte row
+ *     loads).  A group with a member that is only 8-byte aligned runs 8-byte paths instead: slower,
+ *     same bits.  hipMalloc and torch allocations are aligned far beyond this.
+ *   - A pointer into a larger batch is legal: to solve QPs [b0, b0 + B) of arrays that hold more,
+ *     pass every per-QP array advanced by b0 blocks (X + b0*E for a block of E elements, f + b0,
+ *     status + b0, ...) and batch = B.  In QPGPU_LAYOUT_QP_MAJOR any b0 will do (an odd b0 moves an
+ *     array with odd E to 8 mod 16: see above); in QPGPU_LAYOUT_TILED64 b0 must be a multiple of
+ *     64, a whole-tile boundary, and the last tile touched must exist whole.
+ *   - A call writes x, f, status, iters (and x_eq, f_eq, status_eq, u, nact where the entry has
+ *     them) of its own QPs and nothing else: no element before, between or after them, no TILED64
+ *     padding slot, and no input (G only with QPGPU_FLAG_WRITE_FACTOR).  x (and x_eq) of a QP whose
+ *     status is QPGPU_QP_NOT_POSITIVE_DEFINITE is left as it was.
  */
 #ifndef QPGPU_H
 #define QPGPU_H

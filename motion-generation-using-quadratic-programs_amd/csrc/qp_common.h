@@ -352,6 +352,10 @@ struct QpArgs {
 constexpr int kStampSlots = 18;
 // internal QpArgs.flags bit set by the host when CI and ci0 are 16-byte aligned
 constexpr uint32_t kArgAligned16 = 0x80000000u;
+// internal QpArgs.flags bit set by the host when G, g0 and (with p > 0) CE and ce0 are 16-byte
+// aligned: only then does the host launch the lane kernels that stage them by 16-byte LDS-DMA
+// (qp_lane.hip stage_all), otherwise their QPGPU_LANE_UNALIGNED builds (qpgpu_api.cpp launch_lane)
+constexpr uint32_t kArgStage16 = 0x10000000u;
 // internal QpArgs.flags bit: the workspace already holds the setup (qp_panel.hip) — J, x0, f0,
 // c1, c2 and the Cholesky status — so the loop kernel starts at the equality phase
 constexpr uint32_t kSetupDone = 0x40000000u;

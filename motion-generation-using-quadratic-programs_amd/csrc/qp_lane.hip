@@ -36,10 +36,29 @@
 #ifndef QPGPU_LANE_FAST
 #define QPGPU_LANE_FAST 0
 #endif
-#if QPGPU_LANE_FAST
+// The same source built again with QPGPU_LANE_UNALIGNED=1 (qp_lane_u.hip, qp_lane_fast_u.hip) is
+// what the host launches when G, g0, CE or ce0 is not 16-byte aligned (include/qpgpu.h asks for
+// natural alignment only): G, g0, CE and ce0 then reach the LDS staging buffer by per-lane 8-byte
+// copies instead of 16-byte LDS-DMA, everything else is the same code and the same arithmetic.
+// A build of its own, not a branch in these kernels: with the branch in place several N = 8
+// instantiations, which sit at the 512-register limit, gained scratch
+// (profiles/placement/kernel_regs_branch_in_kernel.txt), while this way the aligned kernels are
+// the code they were.  All of its instantiations share one translation unit.
+#ifndef QPGPU_LANE_UNALIGNED
+#define QPGPU_LANE_UNALIGNED 0
+#endif
+#if QPGPU_LANE_FAST && QPGPU_LANE_UNALIGNED
+#define QPK_LANE_NS qpk_fast_u
+#define QP_LANE_KERNEL qp_lane_fast_kernel
+#define QPK_LANE_C(name) name##_fast_u
+#elif QPGPU_LANE_FAST
 #define QPK_LANE_NS qpk_fast
 #define QP_LANE_KERNEL qp_lane_fast_kernel
 #define QPK_LANE_C(name) name##_fast
+#elif QPGPU_LANE_UNALIGNED
+#define QPK_LANE_NS qpk_u
+#define QP_LANE_KERNEL qp_lane_kernel
+#define QPK_LANE_C(name) name##_u
 #else
 #define QPK_LANE_NS qpk
 #define QP_LANE_KERNEL qp_lane_kernel
@@ -186,8 +205,17 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // The wave's 64 QPs occupy [X + b0*E, X + (b0+64)*E) in both layouts (TILED64 arrays hold
   // whole tiles, so its waves are always full).  Staging copies a contiguous span of that
   // range into sbuf with LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no
-  // VGPRs, everything in flight at once); a partial last QP-major wave copies per lane.
+  // VGPRs, everything in flight at once); a partial last QP-major wave copies per lane.  Each
+  // DMA piece is a 16-byte load from X + b0*E + 2*lane + k: 16-byte aligned exactly when X is
+  // (b0*E*8 is a multiple of 512).  The host checks that for G, g0, CE and ce0 (kArgStage16) and
+  // launches these kernels only then; otherwise it launches the QPGPU_LANE_UNALIGNED build, where
+  // every wave copies per lane, 8 bytes at a time, in both layouts.  (Preprocessor, not
+  // `if constexpr`: the aligned build's text stays token for token what it was, and so its code.)
+#if QPGPU_LANE_UNALIGNED
+  const bool full = false;
+#else
   const bool full = (T == 64) || (valid == kQpw);
+#endif
   auto copy_chunk = [&](const double* src, int nd, int off, int k) {  // doubles [k, k+128)
     const int e = k + 2 * lane;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(e < nd ? src + e : src),
@@ -198,6 +226,19 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     for (int k = 0; k < nd; k += 128) copy_chunk(src, nd, off, k);
   };
   // whole tile of X (E doubles per QP) -> sbuf[off...]
+#if QPGPU_LANE_UNALIGNED
+  auto stage_all = [&](const double* X, int E, int off) {
+    if constexpr (T == 64) {
+      // (the tile is whole: the padding slots of a last tile are copied as the DMA copies them)
+      const double* src = X + b0 * (int64_t)E + lane;
+      for (int e = 0; e < E; e++) sbuf[off + e * kQpw + lane] = src[e * kQpw];
+    } else if (live) {
+      const double* src = X + b * (int64_t)E;
+      for (int e = 0; e < E; e++) sbuf[off + lane * E + e] = src[e];
+    }
+  };
+  (void)copy_span;  // (no DMA in this build)
+#else
   auto stage_all = [&](const double* X, int E, int off) {
     if (full) {
       copy_span(X + b0 * (int64_t)E, kQpw * E, off);
@@ -206,6 +247,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       for (int e = 0; e < E; e++) sbuf[off + lane * E + e] = src[e];
     }
   };
+#endif
   auto rd_all = [&](int off, int E, int k) -> double {
     if constexpr (T == 64)
       return sbuf[off + k * 64 + lane];
@@ -1555,7 +1597,7 @@ extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStrea
   if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
   return v->launch(*a, stream);
 }
-#if !QPGPU_LANE_FAST
+#if !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED
 extern "C" const char* qpk_lane_box_name(int n, int /*p*/) {
   const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
   return v ? v->box_name : nullptr;

@@ -29,6 +29,11 @@ extern "C" const char* qpk_lane_name(int n, int p, int m);
 extern "C" hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream, int* handled,
                                            const char** name);
 extern "C" const char* qpk_lane_name_fast(int n, int p, int m);
+// the QPGPU_LANE_UNALIGNED builds of the two (qp_lane_u.hip, qp_lane_fast_u.hip)
+extern "C" hipError_t qpk_launch_lane_u(const qpk::QpArgs* a, hipStream_t stream, int* handled,
+                                        const char** name);
+extern "C" hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream, int* handled,
+                                             const char** name);
 extern "C" hipError_t qpk_launch_medium_ws(const qpk::QpArgs* a, hipStream_t stream, int* handled,
                                            const char** name, double* ws);
 extern "C" int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a);
@@ -205,6 +210,25 @@ const char* qpgpu_kernel_name(int32_t n, int32_t p, int32_t m) {
   return s ? s : "";
 }
 
+// The internal QpArgs.flags bits that license the lane kernel's explicit 16-byte accesses through
+// the caller's pointers (include/qpgpu.h asks for natural alignment only).  One bit per group of
+// arrays, so that an odd g0 does not switch off CI's on-chip copy and an odd ci0 not the staging:
+//   kArgAligned16  CI and ci0: the per-lane LDS-DMA of CI rows, the LDS-resident CI rows and the
+//                  double2 row loads of the l1 scan
+//   kArgStage16    G, g0 and (p > 0) CE, ce0: the per-wave LDS-DMA staging (stage_all / round B)
+// A NULL pointer (an empty array, or CI / ci0 of the box entries) counts as aligned: it is never
+// read through.  Whole tiles and QP blocks of 64 keep every wave's base at the array's residue.
+static uint32_t alignment_flags(const double* G, const double* g0, const double* CE,
+                                const double* ce0, const double* CI, const double* ci0, int32_t p) {
+  auto bits = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  uint32_t f = 0;
+  if (((bits(CI) | bits(ci0)) & 15u) == 0) f |= qpk::kArgAligned16;
+  uintptr_t st = bits(G) | bits(g0);
+  if (p > 0) st |= bits(CE) | bits(ce0);
+  if ((st & 15u) == 0) f |= qpk::kArgStage16;
+  return f;
+}
+
 static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,
                               const double* CE, const double* ce0, const double* CI,
                               const double* ci0, double* x, double* f, int32_t* status,
@@ -374,11 +398,14 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
   std::unique_lock<std::mutex> ws_hold;  // the workspace cache's lock, once a workspace is taken
   a.flags = (d->flags & (QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_EXACT)) | internal;
   const bool fast = (d->flags & QPGPU_FLAG_FAST) != 0;
+  a.flags |= alignment_flags(G, g0, CE, ce0, CI, ci0, d->p);
+  // The lane kernels stage G, g0, CE and ce0 by 16-byte LDS-DMA: launched only when those arrays
+  // are 16-byte aligned, their QPGPU_LANE_UNALIGNED builds (per-lane 8-byte copies) otherwise.
   auto launch_lane = [&]() {
+    if (!(a.flags & qpk::kArgStage16))
+      return fast ? qpk_launch_lane_fast_u(&a, s, &handled, nullptr) : qpk_launch_lane_u(&a, s, &handled, nullptr);
     return fast ? qpk_launch_lane_fast(&a, s, &handled, nullptr) : qpk_launch_lane(&a, s, &handled, nullptr);
   };
-  if (((reinterpret_cast<uintptr_t>(CI) | reinterpret_cast<uintptr_t>(ci0)) & 15u) == 0)
-    a.flags |= qpk::kArgAligned16;
   // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
   // no elements has a NULL data_ptr.  The wave kernels' l1 scan loads element 0 of a clamped
   // constraint index without a predicate and discards the value (qp_wave.hip, "a lane's two
@@ -809,6 +836,17 @@ int qpgpu_debug_shadow_stats(uint64_t* out, int reset) {
 // Test hook (not in include/qpgpu.h): the generic kernel's per-launch workspace cap in bytes
 // (<= 0 restores the 4 GiB default), so the sub-batch path runs on small shapes.
 void qpgpu_debug_set_generic_ws_cap(int64_t bytes) { g_generic_ws_cap = bytes > 0 ? bytes : ((int64_t)4 << 30); }
+
+// Test hook (not in include/qpgpu.h): what the solve entries derive from the addresses of their
+// input arrays (alignment_flags; the pointers are only looked at, never read through).  Bit 0: CI
+// and ci0 are 16-byte aligned (kArgAligned16); bit 1: G, g0 and, with p > 0, CE and ce0 are
+// (kArgStage16).
+int qpgpu_debug_alignment_bits(const void* G, const void* g0, const void* CE, const void* ce0,
+                               const void* CI, const void* ci0, int32_t p) {
+  auto D = [](const void* q) { return static_cast<const double*>(q); };
+  const uint32_t f = alignment_flags(D(G), D(g0), D(CE), D(ce0), D(CI), D(ci0), p);
+  return ((f & qpk::kArgAligned16) ? 1 : 0) | ((f & qpk::kArgStage16) ? 2 : 0);
+}
 
 int qpgpu_relayout(int64_t batch, int32_t elems, const double* src, double* dst, int32_t to_tiled,
                    void* stream) {
