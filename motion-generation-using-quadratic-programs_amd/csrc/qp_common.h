@@ -340,21 +340,28 @@ struct QpArgs {
   uint64_t* stamps;
   // optional (NULL unless qpgpu_solve_batched_dual): the multipliers the reference holds when it
   // returns, dense (p + m per QP, laid out like x), and the number of active inequalities.  A
-  // non-NULL u selects each family's dual instantiation at the launch site.
+  // non-NULL u is the DUAL bit of the launch's mode (mode_of below).
   double* u;
   int32_t* nact;
   // optional (NULL unless qpgpu_solve_batched_box): the bounds lo <= x <= hi, n per QP laid out
-  // like x, standing for CI = [-I, +I], ci0 = [hi; -lo] (m = 2n).  A non-NULL hi selects each
-  // family's box instantiation at the launch site; those kernels never read CI / ci0.
+  // like x, standing for CI = [-I, +I], ci0 = [hi; -lo] (m = 2n).  A non-NULL hi is the BOX bit
+  // of the launch's mode (mode_of below); the box kernels never read CI / ci0.
   const double* hi;
   const double* lo;
 };
 constexpr int kStampSlots = 18;
+
+// The mode of a launch (host side): which of a family's four kernels runs — the kernel bodies'
+// two compile-time booleans, bit 0 DUAL (a.u is set), bit 1 BOX (a.hi is set).  Indexes the name
+// tables of the families' variants; the selection itself is qpgpu_api.cpp select_kernel().
+enum Mode { kPlain = 0, kDual = 1, kBox = 2, kBoxDual = 3 };
+inline Mode mode_of(const QpArgs& a) { return Mode((a.u ? kDual : kPlain) | (a.hi ? kBox : kPlain)); }
+
 // internal QpArgs.flags bit set by the host when CI and ci0 are 16-byte aligned
 constexpr uint32_t kArgAligned16 = 0x80000000u;
 // internal QpArgs.flags bit set by the host when G, g0 and (with p > 0) CE and ce0 are 16-byte
 // aligned: only then does the host launch the lane kernels that stage them by 16-byte LDS-DMA
-// (qp_lane.hip stage_all), otherwise their QPGPU_LANE_UNALIGNED builds (qpgpu_api.cpp launch_lane)
+// (qp_lane.hip stage_all), otherwise their QPGPU_LANE_UNALIGNED builds (qpgpu_api.cpp run)
 constexpr uint32_t kArgStage16 = 0x10000000u;
 // internal QpArgs.flags bit: the workspace already holds the setup (qp_panel.hip) — J, x0, f0,
 // c1, c2 and the Cholesky status — so the loop kernel starts at the equality phase
@@ -418,3 +425,28 @@ __device__ __forceinline__ void qp_stamp(const QpArgs& a, int slot) {
 }
 
 }  // namespace qpk
+
+// ---- what each kernel family exports to qpgpu_api.cpp (the library's internal boundary) ---------
+// One query and one launch per family and build.  *_name: the kernel the family runs for (n, m)
+// in `mode` (a qpk::Mode), NULL where it has none; no family's choice reads p.  qpk_launch_*:
+// enqueue that kernel for *a in mode_of(*a); the caller has asked *_name first, so a shape or
+// mode the build lacks is hipErrorInvalidValue, never a silent success.
+extern "C" {
+const char* qpk_lane_name(int n, int m, int mode);       // qp_lane.hip, the exact build
+const char* qpk_lane_name_fast(int n, int m, int mode);  // ... with QPGPU_LANE_FAST
+hipError_t qpk_launch_lane(const qpk::QpArgs* a, hipStream_t stream);
+hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream);
+// the QPGPU_LANE_UNALIGNED builds of the two, launched when kArgStage16 is not set
+hipError_t qpk_launch_lane_u(const qpk::QpArgs* a, hipStream_t stream);
+hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream);
+const char* qpk_small_name(int n, int m, int mode);  // qp_small.hip
+hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream);
+const char* qpk_medium_name(int n, int m, int mode);       // qp_wave.hip
+const char* qpk_medium_name_fast(int n, int m, int mode);  // ... with QPGPU_WAVE_FAST (LDS variants)
+int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a);  // device workspace of a launch (0 = none)
+hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream, double* ws);
+hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream);
+const char* qpk_generic_name(int n, int m, int mode);  // qp_generic.hip
+int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch);
+hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws);
+}

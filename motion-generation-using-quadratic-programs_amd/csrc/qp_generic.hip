@@ -701,25 +701,34 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_box_dual_kernel(const QpArg
 // Largest shape the generic kernel accepts: n*n and the workspace offsets stay within int64 and a
 // QP's workspace within 2^34 doubles (128 GiB); int32 element indices of the inputs (n*n, n*m).
 // CE offsets (n*p, j*p + i) are computed in int64, so p is not bounded here.
-extern "C" int qpk_generic_covers(int n, int m) {
+static bool generic_covers(int n, int m) {
   return n >= 1 && m >= 0 && (int64_t)n * n < ((int64_t)1 << 31) && (int64_t)n * m < ((int64_t)1 << 31);
 }
 extern "C" int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch) {
   return qpk::gen_lay(n, m).per_qp * 8 * batch;
 }
-extern "C" const char* qpk_generic_name(int n, int /*p*/, int m) {
-  return qpk_generic_covers(n, m) ? "qp_generic<BS=256,global workspace>" : nullptr;
+extern "C" const char* qpk_generic_name(int n, int m, int mode) {
+  static const char* const kNames[4] = {  // by Mode
+      "qp_generic<BS=256,global workspace>", "qp_generic_dual<BS=256,global workspace>",
+      "qp_generic_box<BS=256,global workspace>", "qp_generic_box_dual<BS=256,global workspace>"};
+  return generic_covers(n, m) ? kNames[mode] : nullptr;
 }
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   if (a->batch <= 0) return hipSuccess;
-  if (a->hi && a->u)
-    hipLaunchKernelGGL(qpk::qp_generic_box_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a,
-                       ws);
-  else if (a->hi)
-    hipLaunchKernelGGL(qpk::qp_generic_box_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
-  else if (a->u)
-    hipLaunchKernelGGL(qpk::qp_generic_dual_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
-  else
-    hipLaunchKernelGGL(qpk::qp_generic_kernel, dim3((unsigned)a->batch), dim3(qpk::kGenBS), 0, stream, *a, ws);
+  const dim3 g((unsigned)a->batch), blk(qpk::kGenBS);
+  switch (qpk::mode_of(*a)) {
+    case qpk::kBoxDual:
+      hipLaunchKernelGGL(qpk::qp_generic_box_dual_kernel, g, blk, 0, stream, *a, ws);
+      break;
+    case qpk::kBox:
+      hipLaunchKernelGGL(qpk::qp_generic_box_kernel, g, blk, 0, stream, *a, ws);
+      break;
+    case qpk::kDual:
+      hipLaunchKernelGGL(qpk::qp_generic_dual_kernel, g, blk, 0, stream, *a, ws);
+      break;
+    case qpk::kPlain:
+      hipLaunchKernelGGL(qpk::qp_generic_kernel, g, blk, 0, stream, *a, ws);
+      break;
+  }
   return hipGetLastError();
 }

@@ -1463,32 +1463,34 @@ template <int NM, int MM, int T>
 static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
   const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
   const dim3 g((unsigned)blocks), blk(64);
-  if (a.hi) {  // bounds instead of CI: a box instantiation, or an error
+  // the three other modes run kernels that only the exact build's part 0 / 1 has: elsewhere an error
+  switch (mode_of(a)) {
 #if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
-    if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
-    if (a.u) {  // ... and the multipliers: a box-dual instantiation
-      if (a.n == NM && a.p == 0)
-        hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
-      else
-        hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+    case kBoxDual:
+    case kBox:
+      if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
+      if (a.u) {
+        if (a.n == NM && a.p == 0)
+          hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+        else
+          hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+      } else if (a.n == NM && a.p == 0) {
+        hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+      } else {
+        hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+      }
       return hipSuccess;
-    }
-    if (a.n == NM && a.p == 0)
-      hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
-    else
-      hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
-    return hipSuccess;
+    case kDual:
+      hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
+      return hipSuccess;
 #else
-    return hipErrorInvalidValue;
+    case kBoxDual:
+    case kBox:
+    case kDual:
+      return hipErrorInvalidValue;
 #endif
-  }
-  if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
-#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
-    hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
-    return hipSuccess;
-#else
-    return hipErrorInvalidValue;
-#endif
+    case kPlain:
+      break;
   }
 // A/B builds with one instantiation only refuse every other launch with an error: a launch
 // they skipped silently once returned the previous call's f / status / passes through the host
@@ -1551,17 +1553,18 @@ static hipError_t launch_lane(const QpArgs& a, hipStream_t stream) {
 
 struct LaneVariant {
   int nmax, mmax;
-  const char* name;
+  const char* name[4];  // by Mode; the fast build has the plain kernels only
   hipError_t (*launch)(const QpArgs&, hipStream_t);
-  const char* box_name;       // qpgpu_solve_batched_box (the exact build)
-  const char* box_dual_name;  // qpgpu_solve_batched_box_dual (the exact build)
 };
 
+#if QPGPU_LANE_FAST
+#define QPK_LANE_NAMES(s) {"qp_lane_fast<" s ">", nullptr, nullptr, nullptr}
+#else
+#define QPK_LANE_NAMES(s) {"qp_lane<" s ">", "qp_lane_dual<" s ">", "qp_lane_box<" s ">", "qp_lane_box_dual<" s ">"}
+#endif
 static const LaneVariant kLaneVariants[] = {
-    {7, 14, kFast ? "qp_lane_fast<N=7,M=14>" : "qp_lane<N=7,M=14>", launch_lane<7, 14>, "qp_lane_box<N=7,M=14>",
-     "qp_lane_box_dual<N=7,M=14>"},
-    {8, 16, kFast ? "qp_lane_fast<N=8,M=16>" : "qp_lane<N=8,M=16>", launch_lane<8, 16>, "qp_lane_box<N=8,M=16>",
-     "qp_lane_box_dual<N=8,M=16>"},
+    {7, 14, QPK_LANE_NAMES("N=7,M=14"), launch_lane<7, 14>},
+    {8, 16, QPK_LANE_NAMES("N=8,M=16"), launch_lane<8, 16>},
 };
 
 const LaneVariant* pick_lane(int n, int m) {
@@ -1586,30 +1589,14 @@ extern "C" hipError_t qpk_launch_lane_p0(const qpk::QpArgs* a, hipStream_t strea
   return hipErrorInvalidValue;
 }
 #else
-extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                                  const char** name) {
+extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream) {
   const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(a->n, a->m);
-  if (!v) {
-    *handled = 0;
-    return hipSuccess;
-  }
-  *handled = 1;
-  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
-  return v->launch(*a, stream);
+  return v ? v->launch(*a, stream) : hipErrorInvalidValue;
 }
-#if !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED
-extern "C" const char* qpk_lane_box_name(int n, int /*p*/) {
-  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
-  return v ? v->box_name : nullptr;
-}
-extern "C" const char* qpk_lane_box_dual_name(int n, int /*p*/) {
-  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, 2 * n);
-  return v ? v->box_dual_name : nullptr;
+#if !QPGPU_LANE_UNALIGNED  // an unaligned build runs what its aligned twin names
+extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m, int mode) {
+  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, m);
+  return v ? v->name[mode] : nullptr;
 }
 #endif
-
-extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int /*p*/, int m) {
-  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, m);
-  return v ? v->name : nullptr;
-}
 #endif  // QPGPU_LANE_PART == 2

@@ -105,47 +105,39 @@ struct SmallCfg {
 template <int S, int NM, int MM>
 static hipError_t launch_small(const QpArgs& a, hipStream_t stream) {
   using C = SmallCfg<S, NM, MM>;
-  const int64_t blocks = (a.batch + C::QPW - 1) / C::QPW;
-  if (a.hi && a.u) {
-    hipLaunchKernelGGL((qp_small_box_dual_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
-                       a);
-    return hipGetLastError();
+  const dim3 g((unsigned)((a.batch + C::QPW - 1) / C::QPW)), blk(64);
+  switch (mode_of(a)) {
+    case kBoxDual:
+      hipLaunchKernelGGL((qp_small_box_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
+      break;
+    case kBox:
+      hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), g, blk, 0, stream, a);
+      break;
+    case kDual:
+      hipLaunchKernelGGL((qp_small_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
+      break;
+    case kPlain:
+      hipLaunchKernelGGL((qp_small_kernel<S, NM, MM>), g, blk, 0, stream, a);
+      break;
   }
-  if (a.hi) {
-    hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
-                       a);
-    return hipGetLastError();
-  }
-  if (a.u) {
-    hipLaunchKernelGGL((qp_small_dual_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
-                       a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL((qp_small_kernel<S, NM, MM>), dim3((unsigned)blocks), dim3(64), 0, stream,
-                     a);
   return hipGetLastError();
 }
 
 struct SmallVariant {
   int nmax, mmax;
-  const char* name;
+  const char* name[4];  // by Mode
   hipError_t (*launch)(const QpArgs&, hipStream_t);
-  const char* box_name;
-  const char* box_dual_name;
 };
 
+#define QPK_SMALL_NAMES(s) {"qp_small<" s ">", "qp_small_dual<" s ">", "qp_small_box<" s ">", "qp_small_box_dual<" s ">"}
 static const SmallVariant kSmallVariants[] = {
-    {8, 16, "qp_small<S=8,N=8,M=16>", launch_small<8, 8, 16>, "qp_small_box<S=8,N=8,M=16>",
-     "qp_small_box_dual<S=8,N=8,M=16>"},
-    {8, 32, "qp_small<S=8,N=8,M=32>", launch_small<8, 8, 32>, "qp_small_box<S=8,N=8,M=32>",
-     "qp_small_box_dual<S=8,N=8,M=32>"},
-    {16, 32, "qp_small<S=16,N=16,M=32>", launch_small<16, 16, 32>, "qp_small_box<S=16,N=16,M=32>",
-     "qp_small_box_dual<S=16,N=16,M=32>"},
-    {16, 64, "qp_small<S=16,N=16,M=64>", launch_small<16, 16, 64>, "qp_small_box<S=16,N=16,M=64>",
-     "qp_small_box_dual<S=16,N=16,M=64>"},
+    {8, 16, QPK_SMALL_NAMES("S=8,N=8,M=16"), launch_small<8, 8, 16>},
+    {8, 32, QPK_SMALL_NAMES("S=8,N=8,M=32"), launch_small<8, 8, 32>},
+    {16, 32, QPK_SMALL_NAMES("S=16,N=16,M=32"), launch_small<16, 16, 32>},
+    {16, 64, QPK_SMALL_NAMES("S=16,N=16,M=64"), launch_small<16, 16, 64>},
 };
 
-const SmallVariant* pick_small(int n, int /*p*/, int m) {
+const SmallVariant* pick_small(int n, int m) {
   for (const auto& v : kSmallVariants)
     if (n <= v.nmax && m <= v.mmax) return &v;  // any p: iq never exceeds n
   return nullptr;
@@ -153,28 +145,12 @@ const SmallVariant* pick_small(int n, int /*p*/, int m) {
 
 }  // namespace qpk
 
-// exported to qpgpu_api.cpp (internal linkage boundary of the library)
-extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                       const char** name) {
-  const qpk::SmallVariant* v = qpk::pick_small(a->n, a->p, a->m);
-  if (!v) {
-    *handled = 0;
-    return hipSuccess;
-  }
-  *handled = 1;
-  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
-  return v->launch(*a, stream);
+extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream) {
+  const qpk::SmallVariant* v = qpk::pick_small(a->n, a->m);
+  return v ? v->launch(*a, stream) : hipErrorInvalidValue;
 }
 
-extern "C" const char* qpk_small_name(int n, int p, int m) {
-  const qpk::SmallVariant* v = qpk::pick_small(n, p, m);
-  return v ? v->name : nullptr;
-}
-extern "C" const char* qpk_small_box_name(int n, int p) {
-  const qpk::SmallVariant* v = qpk::pick_small(n, p, 2 * n);
-  return v ? v->box_name : nullptr;
-}
-extern "C" const char* qpk_small_box_dual_name(int n, int p) {
-  const qpk::SmallVariant* v = qpk::pick_small(n, p, 2 * n);
-  return v ? v->box_dual_name : nullptr;
+extern "C" const char* qpk_small_name(int n, int m, int mode) {
+  const qpk::SmallVariant* v = qpk::pick_small(n, m);
+  return v ? v->name[mode] : nullptr;
 }

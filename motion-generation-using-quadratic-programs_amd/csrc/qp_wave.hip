@@ -2615,62 +2615,11 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1
     qp_wave_dual_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, true>(a, ws);
 }
-template <int S, int NMAX, int MMAX, bool GJR>
-static hipError_t launch_wave_dual(const QpArgs& a, hipStream_t stream, double* ws) {
-  using C = WaveCfg<S, NMAX, MMAX, GJR>;
-  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  // the OCC = 1 instantiation's layout: R packed where that one sets up in registers
-  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
-  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
-  if (lds_bytes > 65536) {  // (see launch_wave)
-    static std::mutex mu;
-    static std::map<int, size_t> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& g = granted[dev];
-    if (lds_bytes > g) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_dual_kernel<S, NMAX, MMAX, GJR>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return e;
-      g = lds_bytes;
-    }
-  }
-  hipLaunchKernelGGL((qp_wave_dual_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
-                     stream, a, ws);
-  return hipGetLastError();
-}
 // qpgpu_solve_batched_box: likewise a kernel of its own per variant, the OCC = 1 layout
 template <int S, int NMAX, int MMAX, bool GJR>
 __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
     qp_wave_box_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, false, true>(a, ws);
-}
-template <int S, int NMAX, int MMAX, bool GJR>
-static hipError_t launch_wave_box(const QpArgs& a, hipStream_t stream, double* ws) {
-  using C = WaveCfg<S, NMAX, MMAX, GJR>;
-  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
-  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
-  if (lds_bytes > 65536) {  // (see launch_wave)
-    static std::mutex mu;
-    static std::map<int, size_t> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& g = granted[dev];
-    if (lds_bytes > g) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_box_kernel<S, NMAX, MMAX, GJR>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return e;
-      g = lds_bytes;
-    }
-  }
-  hipLaunchKernelGGL((qp_wave_box_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
-                     stream, a, ws);
-  return hipGetLastError();
 }
 // qpgpu_solve_batched_box_dual: bounds and the multipliers, again a kernel of its own per variant
 template <int S, int NMAX, int MMAX, bool GJR>
@@ -2678,52 +2627,70 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1
     qp_wave_box_dual_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, true, true>(a, ws);
 }
+#endif
+
+// ------------------------------------------------------------------------------------------
+using WaveKernel = void (*)(const QpArgs, double*);
+
+// Dynamic LDS beyond 64 KiB must be granted per kernel and device (callers test bytes > 65536
+// first, so smaller launches never come here).  Host threads may launch concurrently
+// (include/qpgpu.h), so the record of what was granted is locked.
+static hipError_t grant_dynamic_lds(WaveKernel kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> granted;
+  const void* k = reinterpret_cast<const void*>(kernel);
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lk(mu);
+  size_t& g = granted[{k, dev}];
+  if (bytes > g) {
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+    g = bytes;
+  }
+  return hipSuccess;
+}
+
+#if !QPGPU_WAVE_FAST
+// the dual, box and box-dual kernels: the OCC = 1 instantiation's layout, R packed where that one
+// sets up in registers
 template <int S, int NMAX, int MMAX, bool GJR>
-static hipError_t launch_wave_box_dual(const QpArgs& a, hipStream_t stream, double* ws) {
+static hipError_t launch_wave_mode(WaveKernel kernel, const QpArgs& a, hipStream_t stream, double* ws) {
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
   const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
   const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
-  if (lds_bytes > 65536) {  // (see launch_wave)
-    static std::mutex mu;
-    static std::map<int, size_t> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+  if (lds_bytes > 65536) {
+    const hipError_t e = grant_dynamic_lds(kernel, lds_bytes);
     if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& g = granted[dev];
-    if (lds_bytes > g) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return e;
-      g = lds_bytes;
-    }
   }
-  hipLaunchKernelGGL((qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS),
-                     lds_bytes, stream, a, ws);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(C::BS), lds_bytes, stream, a, ws);
   return hipGetLastError();
 }
 #endif
 
-// ------------------------------------------------------------------------------------------
 template <int S, int NMAX, int MMAX, bool GJR>
 static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  if (a.hi) {  // bounds instead of CI: the box instantiation, or an error
+  // the three other modes run kernels that only the exact build has: in the fast build an error
+  switch (mode_of(a)) {
 #if !QPGPU_WAVE_FAST
-    if (a.u) return launch_wave_box_dual<S, NMAX, MMAX, GJR>(a, stream, ws);  // ... and the multipliers
-    return launch_wave_box<S, NMAX, MMAX, GJR>(a, stream, ws);
+    case kBoxDual:
+      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
+    case kBox:
+      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_box_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
+    case kDual:
+      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_dual_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
 #else
-    return hipErrorInvalidValue;
+    case kBoxDual:
+    case kBox:
+    case kDual:
+      return hipErrorInvalidValue;
 #endif
-  }
-  if (a.u) {  // the multipliers are asked for: the dual instantiation, or an error — never without
-#if !QPGPU_WAVE_FAST
-    return launch_wave_dual<S, NMAX, MMAX, GJR>(a, stream, ws);
-#else
-    return hipErrorInvalidValue;
-#endif
+    case kPlain:
+      break;
   }
   size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR).stride * sizeof(double);
   // Two-QP-per-wave variants: when a block's LDS leaves room for >= 2 waves per SIMD (<= 20 KiB,
@@ -2755,22 +2722,9 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
     const size_t want = (size_t)163840 / cap - 1024;
     if (want > lds_bytes) lds_bytes = want;
   }
-  // dynamic LDS beyond 64 KiB must be granted per kernel and device; host threads may launch
-  // concurrently (include/qpgpu.h), so the record of what was granted is locked
   if (lds_bytes > 65536) {
-    static std::mutex mu;
-    static std::map<int, size_t> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = grant_dynamic_lds(QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>, lds_bytes);
     if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(mu);
-    size_t& g = granted[dev];
-    if (lds_bytes > g) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (e != hipSuccess) return e;
-      g = lds_bytes;
-    }
   }
   hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
                      stream, a, ws);
@@ -2780,30 +2734,28 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
 struct WaveVariant {
   int nmax, mmax;
   int64_t ws_doubles_per_qp;
-  const char* name;
+  const char* name[4];  // by Mode; the fast build has the plain kernels only
   hipError_t (*launch)(const QpArgs&, hipStream_t, double*);
-  const char* box_name;
-  const char* box_dual_name;
 };
 
 #if QPGPU_WAVE_FAST
-#define QPK_WAVE_VNAME(s) "qp_wave_fast<" s ">"
+#define QPK_WAVE_NAMES(plain, s) {"qp_wave_fast<" s ">", nullptr, nullptr, nullptr}
 #else
-#define QPK_WAVE_VNAME(s) "qp_wave<" s ">"
+#define QPK_WAVE_NAMES(plain, s) {plain "qp_wave<" s ">", "qp_wave_dual<" s ">", "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"}
 #endif
-#define QPK_WAVE_BNAME(s) "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"
 static const WaveVariant kWaveVariants[] = {
 #if QPGPU_WAVE_S16
-    {16, 32, 0, QPK_WAVE_VNAME("S=16,N=16,M=32"), launch_wave<16, 16, 32, false>, QPK_WAVE_BNAME("S=16,N=16,M=32")},
+    {16, 32, 0, QPK_WAVE_NAMES("", "S=16,N=16,M=32"), launch_wave<16, 16, 32, false>},
 #endif
-    {32, 64, 0, QPK_WAVE_VNAME("S=32,N=32,M=64"), launch_wave<32, 32, 64, false>, QPK_WAVE_BNAME("S=32,N=32,M=64")},
-    {32, 128, 0, QPK_WAVE_VNAME("S=32,N=32,M=128"), launch_wave<32, 32, 128, false>, QPK_WAVE_BNAME("S=32,N=32,M=128")},
-    {64, 128, 0, QPK_WAVE_VNAME("S=64,N=64,M=128"), launch_wave<64, 64, 128, false>, QPK_WAVE_BNAME("S=64,N=64,M=128")},
-    {64, 256, 0, QPK_WAVE_VNAME("S=64,N=64,M=256"), launch_wave<64, 64, 256, false>, QPK_WAVE_BNAME("S=64,N=64,M=256")},
+    {32, 64, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=64"), launch_wave<32, 32, 64, false>},
+    {32, 128, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=128"), launch_wave<32, 32, 128, false>},
+    {64, 128, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=128"), launch_wave<64, 64, 128, false>},
+    {64, 256, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=256"), launch_wave<64, 64, 256, false>},
 #if !QPGPU_WAVE_FAST
+    // (the plain mode's default is the panel path; the other modes always run EXACT, without it)
     {256, 1024, WaveCfg<256, 256, 1024, true>::WS_DOUBLES,
-     "qp_panel<MFMA f64 16x16x4> + qp_wave<S=256,N=256,M=1024,global J/R>",
-     launch_wave<256, 256, 1024, true>, QPK_WAVE_BNAME("S=256,N=256,M=1024,global J/R")},
+     QPK_WAVE_NAMES("qp_panel<MFMA f64 16x16x4> + ", "S=256,N=256,M=1024,global J/R"),
+     launch_wave<256, 256, 1024, true>},
 #endif
 };
 
@@ -2818,33 +2770,18 @@ const WaveVariant* pick_wave(int n, int m) {
 #if QPGPU_WAVE_FAST
 // the fast build covers the LDS variants only (n <= 64, m <= 256); wider shapes keep the
 // default path (its n > 64 form is already the 1e-10 tolerance mode)
-extern "C" const char* qpk_medium_name_fast(int n, int /*p*/, int m) {
+extern "C" const char* qpk_medium_name_fast(int n, int m, int mode) {
   const qpk_wfast::WaveVariant* v = qpk_wfast::pick_wave(n, m);
-  return v ? v->name : nullptr;
+  return v ? v->name[mode] : nullptr;
 }
-extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                             const char** name) {
+extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream) {
   const qpk_wfast::WaveVariant* v = qpk_wfast::pick_wave(a->n, a->m);
-  if (!v) {
-    *handled = 0;
-    return hipSuccess;
-  }
-  *handled = 1;
-  if (name) *name = v->name;
-  return v->launch(*a, stream, nullptr);
+  return v ? v->launch(*a, stream, nullptr) : hipErrorInvalidValue;
 }
 #else
-extern "C" const char* qpk_medium_name(int n, int /*p*/, int m) {
+extern "C" const char* qpk_medium_name(int n, int m, int mode) {
   const qpk::WaveVariant* v = qpk::pick_wave(n, m);
-  return v ? v->name : nullptr;
-}
-extern "C" const char* qpk_medium_box_name(int n, int /*p*/) {
-  const qpk::WaveVariant* v = qpk::pick_wave(n, 2 * n);
-  return v ? v->box_name : nullptr;
-}
-extern "C" const char* qpk_medium_box_dual_name(int n, int /*p*/) {
-  const qpk::WaveVariant* v = qpk::pick_wave(n, 2 * n);
-  return v ? v->box_dual_name : nullptr;
+  return v ? v->name[mode] : nullptr;
 }
 extern "C" int qpk_medium_max_n(void) { return 256; }
 extern "C" int qpk_medium_max_m(void) { return 1024; }
@@ -2881,15 +2818,9 @@ extern "C" int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a) {
   return v ? v->ws_doubles_per_qp * 8 * a->batch + shadow_bytes(v, a) : 0;
 }
 
-extern "C" hipError_t qpk_launch_medium_ws(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                          const char** name, double* ws) {
+extern "C" hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   const qpk::WaveVariant* v = qpk::pick_wave(a->n, a->m);
-  if (!v) {
-    *handled = 0;
-    return hipSuccess;
-  }
-  *handled = 1;
-  if (name) *name = a->hi ? (a->u ? v->box_dual_name : v->box_name) : v->name;
+  if (!v) return hipErrorInvalidValue;
   if (uses_panel(v, a->flags)) {
     hipError_t e = qpk_launch_panel_setup(a, stream, ws);
     if (e != hipSuccess) return e;

@@ -20,37 +20,6 @@
 #include "../../include/qpgpu.h"
 #include "qp_common.h"
 
-extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                       const char** name);
-extern "C" const char* qpk_small_name(int n, int p, int m);
-extern "C" hipError_t qpk_launch_lane(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                      const char** name);
-extern "C" const char* qpk_lane_name(int n, int p, int m);
-extern "C" hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                           const char** name);
-extern "C" const char* qpk_lane_name_fast(int n, int p, int m);
-// the QPGPU_LANE_UNALIGNED builds of the two (qp_lane_u.hip, qp_lane_fast_u.hip)
-extern "C" hipError_t qpk_launch_lane_u(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                        const char** name);
-extern "C" hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                             const char** name);
-extern "C" hipError_t qpk_launch_medium_ws(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                           const char** name, double* ws);
-extern "C" int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a);
-extern "C" const char* qpk_medium_name(int n, int p, int m);
-extern "C" const char* qpk_medium_name_fast(int n, int p, int m);
-extern "C" int qpk_generic_covers(int n, int m);
-extern "C" int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch);
-extern "C" const char* qpk_generic_name(int n, int p, int m);
-extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws);
-extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream, int* handled,
-                                             const char** name);
-extern "C" const char* qpk_lane_box_name(int n, int p);
-extern "C" const char* qpk_small_box_name(int n, int p);
-extern "C" const char* qpk_medium_box_name(int n, int p);
-extern "C" const char* qpk_lane_box_dual_name(int n, int p);
-extern "C" const char* qpk_small_box_dual_name(int n, int p);
-extern "C" const char* qpk_medium_box_dual_name(int n, int p);
 extern "C" int qpk_medium_max_n(void);
 extern "C" int qpk_medium_max_m(void);
 extern "C" hipError_t qpk_relayout(int64_t batch, int E, const double* src, double* dst,
@@ -171,43 +140,72 @@ int qpgpu_max_m(void) {
 static bool default_small(int n, int m) { return n <= 8 && m <= 32; }
 
 // Largest device workspace one generic-kernel launch uses (bytes); larger batches run as
-// sub-batches (solve_batched_impl).  4 GiB; qpgpu_debug_set_generic_ws_cap lowers it in tests.
+// sub-batches (launch_generic).  4 GiB; qpgpu_debug_set_generic_ws_cap lowers it in tests.
 static int64_t g_generic_ws_cap = (int64_t)4 << 30;
 
-const char* qpgpu_kernel_name_flags(int32_t n, int32_t p, int32_t m, uint32_t flags) {
-  if (!flags_valid(flags)) return "";  // the launch would be rejected (QPGPU_ERR_INVALID_ARGUMENT)
-  // the generic family has no fast build: FAST | FORCE_GENERIC launches the generic kernel
-  // (solve_batched_impl), so it is named before the fast builds
-  if (flags & QPGPU_FLAG_FORCE_GENERIC) return qpk_generic_name(n, p, m) ? qpk_generic_name(n, p, m) : "";
-  if ((flags & QPGPU_FLAG_FAST) && n > 0 && p >= 0 && m >= 0) {
-    // the fast builds: the lane kernel's where it covers the shape, else the wave kernel's LDS
-    // variants (n <= 64, m <= 256); a forced family keeps to that family
-    const bool lane_ok = !(flags & (QPGPU_FLAG_FORCE_SUBGROUP | QPGPU_FLAG_FORCE_WAVE));
-    const char* s = lane_ok ? qpk_lane_name_fast(n, p, m) : nullptr;
-    if (s) return s;
-    const bool wave_ok = (flags & QPGPU_FLAG_FORCE_WAVE) ||
-                         (!(flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP)) &&
-                          !qpk_lane_name(n, p, m) && !(default_small(n, m) && qpk_small_name(n, p, m)));
-    s = wave_ok ? qpk_medium_name_fast(n, p, m) : nullptr;
-    if (s) return s;
+// ---- the selection: which kernel runs for (n, p, m, flags, mode) ------------------
+// The one statement of the policy: the name functions, the host entries' coverage check and the
+// launch (run) all ask it.  family == kNone: no kernel — a rejected flag combination or a shape
+// (or mode) the family asked for lacks.
+enum Family { kNone, kLane, kSmall, kWave, kGeneric };
+struct Pick {
+  Family family = kNone;
+  bool fast = false;  // the QPGPU_FLAG_FAST build of the family
+  const char* name = "";
+};
+
+static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode) {
+  if (!flags_valid(flags)) return {};
+  // the fast builds restate the plain kernels only: the other modes refuse QPGPU_FLAG_FAST
+  if ((flags & QPGPU_FLAG_FAST) && mode != qpk::kPlain) return {};
+  const uint32_t force = flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP |
+                                  QPGPU_FLAG_FORCE_WAVE | QPGPU_FLAG_FORCE_GENERIC);
+  // Sizes no launch has (validate): no kernel — except that qpgpu_kernel_name_flags has always
+  // answered with a forced family's exact kernel where that family's table admits them.
+  const bool sized = n > 0 && p >= 0 && m >= 0;
+  if (!sized && (!force || mode != qpk::kPlain)) return {};
+  const bool fast = (flags & QPGPU_FLAG_FAST) && sized;
+  // A forced family keeps to that family; otherwise lane, subgroup (only where default_small),
+  // wave, generic.  With FAST a family's fast build comes first where it covers the shape and its
+  // exact kernels otherwise; the subgroup and generic families have none, so FAST | FORCE_GENERIC
+  // is the generic kernel and a default_small shape takes the subgroup kernel ahead of the fast
+  // wave build.
+  const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
+  const char* s;
+  if (may(QPGPU_FLAG_FORCE_LANE) && (s = fast ? qpk_lane_name_fast(n, m, mode) : qpk_lane_name(n, m, mode)))
+    return {kLane, fast, s};
+  if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name(n, m, mode)))
+    return {kSmall, false, s};
+  if (may(QPGPU_FLAG_FORCE_WAVE)) {
+    if (fast && (s = qpk_medium_name_fast(n, m, mode))) return {kWave, true, s};  // LDS variants (n <= 64, m <= 256)
+    if ((s = qpk_medium_name(n, m, mode))) return {kWave, false, s};
   }
-  if (flags & QPGPU_FLAG_FORCE_LANE) return qpk_lane_name(n, p, m) ? qpk_lane_name(n, p, m) : "";
-  if (flags & QPGPU_FLAG_FORCE_SUBGROUP) return qpk_small_name(n, p, m) ? qpk_small_name(n, p, m) : "";
-  if (flags & QPGPU_FLAG_FORCE_WAVE) return qpk_medium_name(n, p, m) ? qpk_medium_name(n, p, m) : "";
-  if (flags & QPGPU_FLAG_FORCE_GENERIC) return qpk_generic_name(n, p, m) ? qpk_generic_name(n, p, m) : "";
-  return qpgpu_kernel_name(n, p, m);
+  if (may(QPGPU_FLAG_FORCE_GENERIC) && (s = qpk_generic_name(n, m, mode)))
+    return {kGeneric, false, s};  // any other shape (n > 256 or m > 1024)
+  return {};
 }
 
-const char* qpgpu_kernel_name(int32_t n, int32_t p, int32_t m) {
-  if (n <= 0 || p < 0 || m < 0) return "";
-  const char* s = qpk_lane_name(n, p, m);
-  if (s) return s;
-  s = default_small(n, m) ? qpk_small_name(n, p, m) : nullptr;
-  if (s) return s;
-  s = qpk_medium_name(n, p, m);
-  if (s) return s;
-  s = qpk_generic_name(n, p, m);  // any other shape (n > 256 or m > 1024)
-  return s ? s : "";
+const char* qpgpu_kernel_name_flags(int32_t n, int32_t p, int32_t m, uint32_t flags) {
+  return select_kernel(n, p, m, flags, qpk::kPlain).name;
+}
+
+const char* qpgpu_kernel_name(int32_t n, int32_t p, int32_t m) { return select_kernel(n, p, m, 0, qpk::kPlain).name; }
+
+// the box entries' kernels: the selection for (n, p, 2n) in their mode
+static const char* box_kernel_name(int32_t n, int32_t p, uint32_t flags, qpk::Mode mode) {
+  return n > INT32_MAX / 2 ? "" : select_kernel(n, p, 2 * n, flags, mode).name;
+}
+const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags) {
+  return box_kernel_name(n, p, flags, qpk::kBox);
+}
+const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags) {
+  return box_kernel_name(n, p, flags, qpk::kBoxDual);
+}
+
+// Does a kernel cover the shape (the forced family's, if one is forced)?  The host entries check
+// it before any copy is queued.
+static bool family_covers(uint32_t flags, int n, int p, int m) {
+  return select_kernel(n, p, m, flags, qpk::kPlain).family != kNone;
 }
 
 // The internal QpArgs.flags bits that license the lane kernel's explicit 16-byte accesses through
@@ -229,151 +227,20 @@ static uint32_t alignment_flags(const double* G, const double* g0, const double*
   return f;
 }
 
-static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,
-                              const double* CE, const double* ce0, const double* CI,
-                              const double* ci0, double* x, double* f, int32_t* status,
-                              int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
-                              void* stream, uint32_t internal = 0, double* u = nullptr,
-                              int32_t* nact = nullptr, const double* hi = nullptr,
-                              const double* lo = nullptr);
-
-int qpgpu_solve_batched(const qpgpu_problem_desc* d, double* G, const double* g0,
-                        const double* CE, const double* ce0, const double* CI,
-                        const double* ci0, double* x, double* f, int32_t* status,
-                        int32_t* iters, void* stream) {
-  return solve_batched_impl(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters, nullptr, nullptr,
-                            nullptr, stream);
-}
-
-int qpgpu_solve_batched_eq(const qpgpu_problem_desc* d, double* G, const double* g0,
-                           const double* CE, const double* ce0, const double* CI,
-                           const double* ci0, double* x, double* f, int32_t* status,
-                           int32_t* iters, double* x_eq, double* f_eq, int32_t* status_eq,
-                           void* stream) {
-  if (!x_eq || !f_eq || !status_eq) return QPGPU_ERR_INVALID_ARGUMENT;
-  return solve_batched_impl(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters, x_eq, f_eq,
-                            status_eq, stream);
-}
-
-// The multipliers too (include/qpgpu.h).  The dual kernels restate the reference's operation
-// order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps it off the
-// tolerance mode (panel setup, tree sums, certification, re-solve), which has no dual form — and
-// QPGPU_FLAG_FAST is refused.  With p + m == 0 there is nothing to return: the plain kernels run.
-int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
-                             const double* CE, const double* ce0, const double* CI,
-                             const double* ci0, double* x, double* f, int32_t* status,
-                             int32_t* iters, double* u, int32_t* nact, void* stream) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
-  const bool any = (int64_t)d->p + d->m > 0;
-  if (any && !u) return QPGPU_ERR_INVALID_ARGUMENT;
-  qpgpu_problem_desc de = *d;
-  de.flags |= QPGPU_FLAG_EXACT;
-  if (!any) {
-    if (nact && d->batch > 0) {
-      hipError_t e = hipMemsetAsync(nact, 0, (size_t)d->batch * sizeof(int32_t),
-                                    reinterpret_cast<hipStream_t>(stream));
-      if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-    }
-    return solve_batched_impl(&de, G, g0, CE, ce0, CI, ci0, x, f, status, iters, nullptr, nullptr,
-                              nullptr, stream);
-  }
-  return solve_batched_impl(&de, G, g0, CE, ce0, CI, ci0, x, f, status, iters, nullptr, nullptr,
-                            nullptr, stream, 0, u, nact);
-}
-
-// Bounds instead of a dense CI (include/qpgpu.h).  The box kernels restate the reference's
-// operation order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps
-// it off the tolerance mode, which has no box form — and QPGPU_FLAG_FAST is refused.
-// (dual: the names of qpgpu_solve_batched_box_dual's kernels, same conditions and order)
-static const char* box_kernel_name(int32_t n, int32_t p, uint32_t flags, bool dual) {
-  if (!flags_valid(flags) || (flags & QPGPU_FLAG_FAST) || n <= 0 || p < 0 || n > INT32_MAX / 2) return "";
-  const int m = 2 * n;
-  const char* s = nullptr;
-  const char* gen = !qpk_generic_covers(n, m) ? nullptr
-                    : dual                    ? "qp_generic_box_dual<BS=256,global workspace>"
-                                              : "qp_generic_box<BS=256,global workspace>";
-  const auto lane = dual ? qpk_lane_box_dual_name : qpk_lane_box_name;
-  const auto small = dual ? qpk_small_box_dual_name : qpk_small_box_name;
-  const auto medium = dual ? qpk_medium_box_dual_name : qpk_medium_box_name;
-  if (flags & QPGPU_FLAG_FORCE_LANE)
-    s = lane(n, p);
-  else if (flags & QPGPU_FLAG_FORCE_SUBGROUP)
-    s = small(n, p);
-  else if (flags & QPGPU_FLAG_FORCE_WAVE)
-    s = medium(n, p);
-  else if (flags & QPGPU_FLAG_FORCE_GENERIC)
-    s = gen;
-  else {  // the plain entry's order for (n, p, 2n)
-    s = lane(n, p);
-    if (!s && default_small(n, m)) s = small(n, p);
-    if (!s) s = medium(n, p);
-    if (!s) s = gen;
-  }
-  return s ? s : "";
-}
-
-const char* qpgpu_kernel_name_box(int32_t n, int32_t p, uint32_t flags) {
-  return box_kernel_name(n, p, flags, false);
-}
-const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags) {
-  return box_kernel_name(n, p, flags, true);
-}
-
-int qpgpu_solve_batched_box(const qpgpu_problem_desc* d, double* G, const double* g0,
-                            const double* CE, const double* ce0, const double* hi,
-                            const double* lo, double* x, double* f, int32_t* status,
-                            int32_t* iters, void* stream) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
-  if ((int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->batch > 0 && (!hi || !lo)) return QPGPU_ERR_INVALID_ARGUMENT;
-  qpgpu_problem_desc de = *d;
-  de.flags |= QPGPU_FLAG_EXACT;
-  return solve_batched_impl(&de, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters, nullptr,
-                            nullptr, nullptr, stream, 0, nullptr, nullptr, hi, lo);
-}
-
-// Bounds and the multipliers (include/qpgpu.h): the union of the two entries' rules above.  With
-// hi and u both set every family launches its box-dual kernel; no CI is written anywhere.
-int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
-                                 const double* CE, const double* ce0, const double* hi,
-                                 const double* lo, double* x, double* f, int32_t* status,
-                                 int32_t* iters, double* u, int32_t* nact, void* stream) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
-  if ((int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->batch > 0 && (!hi || !lo)) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (!u) return QPGPU_ERR_INVALID_ARGUMENT;  // p + 2n > 0 always
-  qpgpu_problem_desc de = *d;
-  de.flags |= QPGPU_FLAG_EXACT;
-  return solve_batched_impl(&de, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters, nullptr,
-                            nullptr, nullptr, stream, 0, u, nact, hi, lo);
-}
-
-static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const double* g0,
-                              const double* CE, const double* ce0, const double* CI,
-                              const double* ci0, double* x, double* f, int32_t* status,
-                              int32_t* iters, double* x_eq, double* f_eq, int32_t* st_eq,
-                              void* stream, uint32_t internal, double* u, int32_t* nact,
-                              const double* hi, const double* lo) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->batch == 0) return QPGPU_SUCCESS;
-  if (!G || !g0 || !x || !f || !status) return QPGPU_ERR_INVALID_ARGUMENT;
-  if ((d->p > 0 && (!CE || !ce0)) || (!hi && d->m > 0 && (!CI || !ci0)))
-    return QPGPU_ERR_INVALID_ARGUMENT;
-  qpk::QpArgs a;
+// The kernels' argument from a validated descriptor and the arrays every entry has, as the caller
+// passed them (the alignment bits are theirs).  An entry then sets its own optional members by
+// name — x_eq / f_eq / st_eq, u / nact, hi / lo (CI and ci0 NULL) — and calls run().
+static qpk::QpArgs make_args(const qpgpu_problem_desc* d, double* G, const double* g0, const double* CE,
+                             const double* ce0, const double* CI, const double* ci0, double* x, double* f,
+                             int32_t* status, int32_t* iters) {
+  qpk::QpArgs a = {};
   a.n = d->n;
   a.p = d->p;
   a.m = d->m;
   a.max_steps = d->max_iter > 0 ? d->max_iter : default_max_steps(d->n, d->p, d->m);
   a.batch = d->batch;
   a.tile = d->layout == QPGPU_LAYOUT_TILED64 ? 64 : 1;
-  a.flags = d->flags;
+  a.flags = (d->flags & (QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_EXACT)) | alignment_flags(G, g0, CE, ce0, CI, ci0, d->p);
   a.G = G;
   a.g0 = g0;
   a.CE = CE;
@@ -384,124 +251,207 @@ static int solve_batched_impl(const qpgpu_problem_desc* d, double* G, const doub
   a.f = f;
   a.status = status;
   a.iters = iters;
-  a.x_eq = x_eq;
-  a.f_eq = f_eq;
-  a.st_eq = st_eq;
   a.stamps = g_stamps;
-  a.u = u;
-  a.nact = nact;
-  a.hi = hi;  // non-NULL: the box kernels, which never read CI / ci0 (left at g0 below)
-  a.lo = lo;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int handled = 0;
-  hipError_t e = hipSuccess;
-  std::unique_lock<std::mutex> ws_hold;  // the workspace cache's lock, once a workspace is taken
-  a.flags = (d->flags & (QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_EXACT)) | internal;
-  const bool fast = (d->flags & QPGPU_FLAG_FAST) != 0;
-  a.flags |= alignment_flags(G, g0, CE, ce0, CI, ci0, d->p);
-  // The lane kernels stage G, g0, CE and ce0 by 16-byte LDS-DMA: launched only when those arrays
-  // are 16-byte aligned, their QPGPU_LANE_UNALIGNED builds (per-lane 8-byte copies) otherwise.
-  auto launch_lane = [&]() {
-    if (!(a.flags & qpk::kArgStage16))
-      return fast ? qpk_launch_lane_fast_u(&a, s, &handled, nullptr) : qpk_launch_lane_u(&a, s, &handled, nullptr);
-    return fast ? qpk_launch_lane_fast(&a, s, &handled, nullptr) : qpk_launch_lane(&a, s, &handled, nullptr);
-  };
-  // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
-  // no elements has a NULL data_ptr.  The wave kernels' l1 scan loads element 0 of a clamped
-  // constraint index without a predicate and discards the value (qp_wave.hip, "a lane's two
-  // constraints"), which faulted on NULL: give the kernels readable memory instead — g0, whose
-  // first element of every QP block (or tile) exists in both layouts.
-  if (!a.CE) a.CE = g0;
-  if (!a.ce0) a.ce0 = g0;
-  if (!a.CI) a.CI = g0;
-  if (!a.ci0) a.ci0 = g0;
-  auto launch_wave = [&]() -> int {
-    if (fast) {
-      e = qpk_launch_medium_fast(&a, s, &handled, nullptr);  // LDS variants (n <= 64, m <= 256)
-      if (handled) return QPGPU_SUCCESS;
-    }
-    double* ws = nullptr;
-    const int wrc = device_workspace(qpk_medium_workspace_bytes(&a), s, &ws, ws_hold);
-    if (wrc) return wrc;
-    e = qpk_launch_medium_ws(&a, s, &handled, nullptr, ws);
-    return QPGPU_SUCCESS;
-  };
-  // The generic kernel's workspace is per QP (2n^2 + 12n + 2m doubles): a large shape launches
-  // over sub-batches whose workspace stays within g_generic_ws_cap (one allocation reused by every
-  // sub-batch in stream order), instead of one allocation for the whole batch — n = 2000 over
-  // 1000 QPs would otherwise ask for ~64 GB and keep it cached.  TILED64 sub-batches are whole
-  // 64-QP tiles, so each one's arrays start at a tile boundary.
-  auto launch_generic = [&]() -> int {
-    if (!qpk_generic_covers(a.n, a.m)) return QPGPU_SUCCESS;  // handled stays 0
-    const int64_t per = qpk_generic_workspace_bytes(a.n, a.m, 1);
-    if (per <= 0) return QPGPU_SUCCESS;  // handled stays 0
-    int64_t chunk = a.batch;
-    if (a.batch > g_generic_ws_cap / per) {  // per * batch > cap, without the int64 overflow
-      chunk = g_generic_ws_cap / per;
-      if (a.tile == 64) chunk = chunk / 64 * 64;
-      if (chunk < (a.tile == 64 ? 64 : 1)) chunk = a.tile == 64 ? 64 : 1;
-    }
-    double* ws = nullptr;
-    const int wrc = device_workspace(per * (chunk < a.batch ? chunk : a.batch), s, &ws, ws_hold);
-    if (wrc) return wrc;
-    handled = 1;
-    const int64_t n = a.n, p = a.p, m = a.m;
-    auto off = [&](int64_t b0, int64_t E) { return a.tile == 64 ? (b0 / 64) * 64 * E : b0 * E; };
-    for (int64_t b0 = 0; b0 < a.batch; b0 += chunk) {
-      qpk::QpArgs c = a;
-      c.batch = (a.batch - b0 < chunk) ? a.batch - b0 : chunk;
-      c.G = a.G + off(b0, n * n);
-      c.g0 = a.g0 + off(b0, n);
-      if (a.CE) c.CE = a.CE + off(b0, n * p);
-      if (a.ce0) c.ce0 = a.ce0 + off(b0, p);
-      if (a.CI) c.CI = a.CI + off(b0, n * m);
-      if (a.ci0) c.ci0 = a.ci0 + off(b0, m);
-      c.x = a.x + off(b0, n);
-      c.f = a.f + b0;
-      c.status = a.status + b0;
-      if (a.iters) c.iters = a.iters + b0;
-      if (a.x_eq) c.x_eq = a.x_eq + off(b0, n);
-      if (a.f_eq) c.f_eq = a.f_eq + b0;
-      if (a.st_eq) c.st_eq = a.st_eq + b0;
-      if (a.u) c.u = a.u + off(b0, p + m);
-      if (a.nact) c.nact = a.nact + b0;
-      if (a.hi) c.hi = a.hi + off(b0, n);
-      if (a.lo) c.lo = a.lo + off(b0, n);
-      if (a.hi) c.CI = c.ci0 = c.g0;  // (never read; kept inside an array of this sub-batch)
-      c.stamps = nullptr;
-      e = qpk_launch_generic(&c, s, ws);
-      if (e != hipSuccess) break;
-    }
-    return QPGPU_SUCCESS;
-  };
-  int wrc = QPGPU_SUCCESS;
-  if (d->flags & QPGPU_FLAG_FORCE_GENERIC) {
-    wrc = launch_generic();
-  } else if (d->flags & QPGPU_FLAG_FORCE_LANE) {
-    e = launch_lane();
-  } else if (d->flags & QPGPU_FLAG_FORCE_SUBGROUP) {
-    e = qpk_launch_small(&a, s, &handled, nullptr);
-  } else if (d->flags & QPGPU_FLAG_FORCE_WAVE) {
-    wrc = launch_wave();
-  } else {
-    e = launch_lane();
-    if (!handled && default_small(a.n, a.m)) e = qpk_launch_small(&a, s, &handled, nullptr);
-    if (!handled) wrc = launch_wave();
-    if (!wrc && !handled) wrc = launch_generic();
+  return a;
+}
+
+// QPs [b0, b0 + count) of a's batch: every per-QP pointer advanced to QP b0's block in a's layout
+// (TILED64: b0 a multiple of 64, so a whole-tile boundary), NULL left NULL.
+static qpk::QpArgs sub_range(const qpk::QpArgs& a, int64_t b0, int64_t count) {
+  const int64_t n = a.n, p = a.p, m = a.m;
+  const auto blocks = [&](auto* q, int64_t E) { return q ? q + (a.tile == 64 ? b0 / 64 * 64 * E : b0 * E) : q; };
+  const auto each = [&](auto* q) { return q ? q + b0 : q; };
+  qpk::QpArgs c = a;
+  c.batch = count;
+  c.G = blocks(a.G, n * n);
+  c.g0 = blocks(a.g0, n);
+  c.CE = blocks(a.CE, n * p);
+  c.ce0 = blocks(a.ce0, p);
+  c.CI = blocks(a.CI, n * m);
+  c.ci0 = blocks(a.ci0, m);
+  c.x = blocks(a.x, n);
+  c.f = each(a.f);
+  c.status = each(a.status);
+  c.iters = each(a.iters);
+  c.x_eq = blocks(a.x_eq, n);
+  c.f_eq = each(a.f_eq);
+  c.st_eq = each(a.st_eq);
+  c.u = blocks(a.u, p + m);
+  c.nact = each(a.nact);
+  c.hi = blocks(a.hi, n);
+  c.lo = blocks(a.lo, n);
+  return c;
+}
+
+// The generic kernel's workspace is per QP (2n^2 + 12n + 2m doubles): a large shape launches
+// over sub-batches whose workspace stays within g_generic_ws_cap (one allocation reused by every
+// sub-batch in stream order), instead of one allocation for the whole batch — n = 2000 over
+// 1000 QPs would otherwise ask for ~64 GB and keep it cached.  TILED64 sub-batches are whole
+// 64-QP tiles, so each one's arrays start at a tile boundary.
+static int launch_generic(const qpk::QpArgs& a, hipStream_t s, std::unique_lock<std::mutex>& ws_hold) {
+  const int64_t per = qpk_generic_workspace_bytes(a.n, a.m, 1);
+  int64_t chunk = a.batch;
+  if (a.batch > g_generic_ws_cap / per) {  // per * batch > cap, without the int64 overflow
+    chunk = g_generic_ws_cap / per;
+    if (a.tile == 64) chunk = chunk / 64 * 64;
+    if (chunk < (a.tile == 64 ? 64 : 1)) chunk = a.tile == 64 ? 64 : 1;
   }
-  if (wrc) return wrc;
-  if (!handled) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  double* ws = nullptr;
+  const int rc = device_workspace(per * (chunk < a.batch ? chunk : a.batch), s, &ws, ws_hold);
+  if (rc) return rc;
+  for (int64_t b0 = 0; b0 < a.batch; b0 += chunk) {
+    qpk::QpArgs c = sub_range(a, b0, a.batch - b0 < chunk ? a.batch - b0 : chunk);
+    if (c.hi) c.CI = c.ci0 = c.g0;  // (never read; kept inside an array of this sub-batch)
+    c.stamps = nullptr;
+    const hipError_t e = qpk_launch_generic(&c, s, ws);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  }
+  return QPGPU_SUCCESS;
+}
+
+// What every device-pointer entry ends in, after validate(d) and its own rules: the empty batch,
+// the NULL checks of the common arrays, the selection, the launch.
+static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream) {
+  if (d->batch == 0) return QPGPU_SUCCESS;
+  if (!a.G || !a.g0 || !a.x || !a.f || !a.status) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((a.p > 0 && (!a.CE || !a.ce0)) || (!a.hi && a.m > 0 && (!a.CI || !a.ci0)))
+    return QPGPU_ERR_INVALID_ARGUMENT;
+  const Pick k = select_kernel(a.n, a.p, a.m, d->flags, qpk::mode_of(a));
+  if (k.family == kNone) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
+  // no elements has a NULL data_ptr; the box kernels never read CI / ci0.  The wave kernels' l1
+  // scan loads element 0 of a clamped constraint index without a predicate and discards the value
+  // (qp_wave.hip, "a lane's two constraints"), which faulted on NULL: give the kernels readable
+  // memory instead — g0, whose first element of every QP block (or tile) exists in both layouts.
+  if (!a.CE) a.CE = a.g0;
+  if (!a.ce0) a.ce0 = a.g0;
+  if (!a.CI) a.CI = a.g0;
+  if (!a.ci0) a.ci0 = a.g0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  std::unique_lock<std::mutex> ws_hold;  // the workspace cache's lock, until the launches are enqueued
+  hipError_t e = hipSuccess;
+  switch (k.family) {
+    case kLane:
+      // The lane kernels stage G, g0, CE and ce0 by 16-byte LDS-DMA: launched only when those arrays
+      // are 16-byte aligned, their QPGPU_LANE_UNALIGNED builds (per-lane 8-byte copies) otherwise.
+      if (a.flags & qpk::kArgStage16)
+        e = k.fast ? qpk_launch_lane_fast(&a, s) : qpk_launch_lane(&a, s);
+      else
+        e = k.fast ? qpk_launch_lane_fast_u(&a, s) : qpk_launch_lane_u(&a, s);
+      break;
+    case kSmall:
+      e = qpk_launch_small(&a, s);
+      break;
+    case kWave:
+      if (k.fast) {
+        e = qpk_launch_medium_fast(&a, s);
+      } else {
+        double* ws = nullptr;
+        const int rc = device_workspace(qpk_medium_workspace_bytes(&a), s, &ws, ws_hold);
+        if (rc) return rc;
+        e = qpk_launch_medium(&a, s, ws);
+      }
+      break;
+    case kGeneric:
+      return launch_generic(a, s, ws_hold);
+    case kNone:
+      break;
+  }
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
   return QPGPU_SUCCESS;
 }
 
-// Does the forced kernel family (if any) cover the shape?  Checked before any copy is queued.
-static bool family_covers(uint32_t flags, int n, int p, int m) {
-  if (flags & QPGPU_FLAG_FORCE_LANE) return qpk_lane_name(n, p, m) != nullptr;
-  if (flags & QPGPU_FLAG_FORCE_SUBGROUP) return qpk_small_name(n, p, m) != nullptr;
-  if (flags & QPGPU_FLAG_FORCE_WAVE) return qpk_medium_name(n, p, m) != nullptr;
-  if (flags & QPGPU_FLAG_FORCE_GENERIC) return qpk_generic_covers(n, m) != 0;
-  return qpgpu_kernel_name(n, p, m)[0] != 0;
+int qpgpu_solve_batched(const qpgpu_problem_desc* d, double* G, const double* g0,
+                        const double* CE, const double* ce0, const double* CI,
+                        const double* ci0, double* x, double* f, int32_t* status,
+                        int32_t* iters, void* stream) {
+  const int rc = validate(d);
+  if (rc) return rc;
+  return run(d, make_args(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters), stream);
+}
+
+int qpgpu_solve_batched_eq(const qpgpu_problem_desc* d, double* G, const double* g0,
+                           const double* CE, const double* ce0, const double* CI,
+                           const double* ci0, double* x, double* f, int32_t* status,
+                           int32_t* iters, double* x_eq, double* f_eq, int32_t* status_eq,
+                           void* stream) {
+  const int rc = validate(d);
+  if (rc) return rc;
+  if (!x_eq || !f_eq || !status_eq) return QPGPU_ERR_INVALID_ARGUMENT;
+  qpk::QpArgs a = make_args(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters);
+  a.x_eq = x_eq;
+  a.f_eq = f_eq;
+  a.st_eq = status_eq;
+  return run(d, a, stream);
+}
+
+// The multipliers too (include/qpgpu.h).  The dual kernels restate the reference's operation
+// order only, so the call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps it off the
+// tolerance mode (panel setup, tree sums, certification, re-solve), which has no dual form — and
+// QPGPU_FLAG_FAST is refused.  With p + m == 0 there is nothing to return: the plain kernels run.
+int qpgpu_solve_batched_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
+                             const double* CE, const double* ce0, const double* CI,
+                             const double* ci0, double* x, double* f, int32_t* status,
+                             int32_t* iters, double* u, int32_t* nact, void* stream) {
+  const int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
+  const bool any = (int64_t)d->p + d->m > 0;
+  if (any && !u) return QPGPU_ERR_INVALID_ARGUMENT;
+  qpk::QpArgs a = make_args(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters);
+  a.flags |= QPGPU_FLAG_EXACT;
+  if (any) {
+    a.u = u;
+    a.nact = nact;
+  } else if (nact && d->batch > 0) {
+    hipError_t e = hipMemsetAsync(nact, 0, (size_t)d->batch * sizeof(int32_t),
+                                  reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+  }
+  return run(d, a, stream);
+}
+
+// Bounds instead of a dense CI (include/qpgpu.h), and with the multipliers (box_dual): the rules
+// the two entries share.  The box kernels restate the reference's operation order only, so the
+// call runs as if QPGPU_FLAG_EXACT were set — for n > 64 that keeps it off the tolerance mode,
+// which has no box form — and QPGPU_FLAG_FAST is refused.
+static int box_rules(const qpgpu_problem_desc* d, const double* hi, const double* lo) {
+  const int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & QPGPU_FLAG_FAST) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0 && (!hi || !lo)) return QPGPU_ERR_INVALID_ARGUMENT;
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_solve_batched_box(const qpgpu_problem_desc* d, double* G, const double* g0,
+                            const double* CE, const double* ce0, const double* hi,
+                            const double* lo, double* x, double* f, int32_t* status,
+                            int32_t* iters, void* stream) {
+  const int rc = box_rules(d, hi, lo);
+  if (rc) return rc;
+  qpk::QpArgs a = make_args(d, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters);
+  a.flags |= QPGPU_FLAG_EXACT;
+  a.hi = hi;
+  a.lo = lo;
+  return run(d, a, stream);
+}
+
+// With hi and u both set every family launches its box-dual kernel; no CI is written anywhere.
+int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d, double* G, const double* g0,
+                                 const double* CE, const double* ce0, const double* hi,
+                                 const double* lo, double* x, double* f, int32_t* status,
+                                 int32_t* iters, double* u, int32_t* nact, void* stream) {
+  const int rc = box_rules(d, hi, lo);
+  if (rc) return rc;
+  if (!u) return QPGPU_ERR_INVALID_ARGUMENT;  // p + 2n > 0 always
+  qpk::QpArgs a = make_args(d, G, g0, CE, ce0, nullptr, nullptr, x, f, status, iters);
+  a.flags |= QPGPU_FLAG_EXACT;
+  a.hi = hi;
+  a.lo = lo;
+  a.u = u;
+  a.nact = nact;
+  return run(d, a, stream);
 }
 
 
@@ -615,12 +565,19 @@ int qpgpu_solve_batched_host(const qpgpu_problem_desc* d, double* G, const doubl
     // f | status | iters poisoned (NaN, -1, -1) and sent with the inputs: outputs a kernel did
     // not write never come back as the previous call's values from the reused device buffer
     std::memset(h + of, 0xFF, total - of);
+    // the outputs from the staging buffer to the caller's arrays, once the stream has completed
+    auto copy_back = [&] {
+      std::memcpy(x, h + ox, nx);
+      std::memcpy(f, h + of, nf);
+      std::memcpy(status, h + os, ns);
+      if (iters) std::memcpy(iters, h + oi, ni);
+      if (wf) std::memcpy(G, h + oG, nG);
+    };
     if (total <= g_zero_copy_bytes && d->p > 0) {
       // zero-copy: the kernel works on the mapped staging buffer directly
       auto Hp = [&](size_t off) { return reinterpret_cast<double*>(h + off); };
-      rc = solve_batched_impl(d, Hp(oG), Hp(og0), Hp(oCE), Hp(oce0), Hp(oCI), Hp(oci0), Hp(ox), Hp(of),
-                              reinterpret_cast<int32_t*>(h + os), reinterpret_cast<int32_t*>(h + oi),
-                              nullptr, nullptr, nullptr, s);
+      rc = qpgpu_solve_batched(d, Hp(oG), Hp(og0), Hp(oCE), Hp(oce0), Hp(oCI), Hp(oci0), Hp(ox), Hp(of),
+                               reinterpret_cast<int32_t*>(h + os), reinterpret_cast<int32_t*>(h + oi), s);
       if (rc) {
         (void)hipStreamSynchronize(s);
         return rc;
@@ -634,11 +591,7 @@ int qpgpu_solve_batched_host(const qpgpu_problem_desc* d, double* G, const doubl
       // A hipStreamQuery spin measured slower than the blocking sync (39.2 vs 36.8 us per C1 call,
       // profiles/r06_s27/latency_parts.log).
       if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-      std::memcpy(x, h + ox, nx);
-      std::memcpy(f, h + of, nf);
-      std::memcpy(status, h + os, ns);
-      if (iters) std::memcpy(iters, h + oi, ni);
-      if (wf) std::memcpy(G, h + oG, nG);
+      copy_back();
       return QPGPU_SUCCESS;
     }
     if ((e = hipMemcpyAsync(base, h, total, hipMemcpyHostToDevice, s)) != hipSuccess)
@@ -655,11 +608,7 @@ int qpgpu_solve_batched_host(const qpgpu_problem_desc* d, double* G, const doubl
     if (wf && (e = hipMemcpyAsync(h + oG, base + oG, nG, hipMemcpyDeviceToHost, s)) != hipSuccess)
       return fail_drain(e, "hipMemcpyAsync D2H");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    std::memcpy(x, h + ox, nx);
-    std::memcpy(f, h + of, nf);
-    std::memcpy(status, h + os, ns);
-    if (iters) std::memcpy(iters, h + oi, ni);
-    if (wf) std::memcpy(G, h + oG, nG);
+    copy_back();
     return QPGPU_SUCCESS;
   }
   auto h2d = [&](size_t off, const void* src, size_t bytes) -> hipError_t {
@@ -763,7 +712,7 @@ int qpgpu_solve_batched_multi(const qpgpu_problem_desc* d, int32_t ndev, const i
   if ((d->p > 0 && (!CE || !ce0)) || (d->m > 0 && (!CI || !ci0))) return QPGPU_ERR_INVALID_ARGUMENT;
   if (!family_covers(d->flags, d->n, d->p, d->m)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   const bool tiled = d->layout == QPGPU_LAYOUT_TILED64;
-  const int64_t B = d->batch, n = d->n, p = d->p, m = d->m;
+  const int64_t B = d->batch;
   // shard bounds: contiguous, whole tiles in TILED64 (a shard may come out empty)
   std::vector<int64_t> lo(ndev + 1);
   for (int k = 0; k <= ndev; k++) {
@@ -771,23 +720,21 @@ int qpgpu_solve_batched_multi(const qpgpu_problem_desc* d, int32_t ndev, const i
     if (tiled) b = (b + 63) / 64 * 64;
     lo[k] = b < B ? b : B;
   }
-  auto off = [&](int64_t b0, int64_t E) { return tiled ? (b0 / 64) * 64 * E : b0 * E; };
+  const qpk::QpArgs all = make_args(d, G, g0, CE, ce0, CI, ci0, x, f, status, iters);
   std::lock_guard<std::mutex> pool_hold(g_pool_mu);
   while ((int)g_pool.size() < ndev) g_pool.emplace_back(new ShardWorker());
   std::vector<int> used;
   for (int k = 0; k < ndev; k++) {
-    const int64_t b0 = lo[k], cnt = lo[k + 1] - lo[k];
+    const int64_t cnt = lo[k + 1] - lo[k];
     if (cnt <= 0) continue;
     qpgpu_problem_desc dk = *d;
     dk.batch = cnt;
+    const qpk::QpArgs c = sub_range(all, lo[k], cnt);
     const int dev = devices[k];
     g_pool[k]->submit([=]() -> int {
       hipError_t e = hipSetDevice(dev);
       if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-      return qpgpu_solve_batched_host(&dk, G + off(b0, n * n), g0 + off(b0, n), CE ? CE + off(b0, n * p) : CE,
-                                      ce0 ? ce0 + off(b0, p) : ce0, CI ? CI + off(b0, n * m) : CI,
-                                      ci0 ? ci0 + off(b0, m) : ci0, x + off(b0, n), f + b0, status + b0,
-                                      iters ? iters + b0 : iters);
+      return qpgpu_solve_batched_host(&dk, c.G, c.g0, c.CE, c.ce0, c.CI, c.ci0, c.x, c.f, c.status, c.iters);
     });
     used.push_back(k);
   }

@@ -441,71 +441,55 @@ def solve_batched_host(pr: Problems, write_factor: bool = False, max_iter: int =
 # ----------------------------------------------------------------------------------------------
 # device-pointer solve (torch tensors already resident in HBM)
 # ----------------------------------------------------------------------------------------------
-class DeviceBatch:
-    """Device-resident inputs/outputs for repeated solves (torch tensors on one GPU)."""
+class _DeviceBatchBase:
+    """What DeviceBatch and DeviceBoxBatch share: the device tensors, the prebuilt ctypes arguments
+    and the results.  A subclass names its six input attributes (_INPUTS: the order of its
+    problem container's arrays() and of the C entries' arguments) and its two C entries."""
 
-    def __init__(self, pr: Problems, device, with_iters: bool = True, layout=None):
+    _INPUTS = ()
+    _ENTRY = _ENTRY_DUAL = None
+
+    def __init__(self, pr, device, with_iters: bool = True, layout=None):
         import torch
 
         self.n, self.p, self.m, self.batch = pr.n, pr.p, pr.m, pr.batch
         self.layout = LAYOUTS[layout]
         conv = to_tiled64 if self.layout == LAYOUT_TILED64 else (lambda a: a)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(conv(np.asarray(a, dtype=np.float64)))).to(device)
-        self.G, self.g0, self.CE, self.ce0, self.CI, self.ci0 = (t(a) for a in pr.arrays())
+        for name, a in zip(self._INPUTS, pr.arrays()):
+            setattr(self, name, t(a))
         rows = (self.batch + 63) // 64 * 64 if self.layout == LAYOUT_TILED64 else self.batch
         self.x = torch.zeros((rows, self.n), dtype=torch.float64, device=device)
         self.f = torch.zeros(self.batch, dtype=torch.float64, device=device)
         self.status = torch.zeros(self.batch, dtype=torch.int32, device=device)
         self.iters = torch.zeros(self.batch, dtype=torch.int32, device=device) if with_iters else None
 
-    def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
-              eq_out=None, exact: bool = False, fast: bool = False, dual_out=None):
-        """Enqueue one batched solve on `stream` (a torch.cuda.Stream, default current).
-        eq_out=(x_eq, f_eq, status_eq) tensors also receive the m = 0 answer
-        (qpgpu_solve_batched_eq).  dual_out=(u, nact) tensors receive the multipliers, p + m
-        float64 per QP in this batch's layout, and the int32 active-inequality counts
-        (qpgpu_solve_batched_dual: reference operation order always; either may be None where
-        the C entry takes NULL).  eq_out and dual_out are separate entries: not both."""
+    def _args(self, stream, max_iter, flags, extra=()):
+        """(descriptor, ctypes arguments) of a C entry: the inputs, the four outputs, the entry's
+        `extra` output tensors, the stream."""
+        d = ProblemDesc(self.n, self.p, self.m, max_iter, self.batch, flags, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        tensors = [getattr(self, k) for k in self._INPUTS] + [self.x, self.f, self.status, self.iters]
+        return d, (ctypes.byref(d), *[vp(t) for t in tensors], *[vp(t) for t in extra],
+                   ctypes.c_void_p(stream.cuda_stream))
+
+    def _solve(self, stream, max_iter, flags, dual_out=None):
         import torch
 
         if stream is None:
             stream = torch.cuda.current_stream(self.x.device)
-        d = ProblemDesc(self.n, self.p, self.m, max_iter, self.batch,
-                        (FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family]
-                        | (FLAG_EXACT if exact else 0) | (FLAG_FAST if fast else 0), self.layout)
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        args = [ctypes.byref(d), vp(self.G), vp(self.g0), vp(self.CE), vp(self.ce0), vp(self.CI),
-                vp(self.ci0), vp(self.x), vp(self.f), vp(self.status), vp(self.iters)]
-        if dual_out is not None:
-            if eq_out is not None:
-                raise ValueError("eq_out and dual_out are separate entry points: pass one")
-            u, nact = dual_out
-            rc = LIB.qpgpu_solve_batched_dual(*args, vp(u), vp(nact), ctypes.c_void_p(stream.cuda_stream))
-            _check(rc, "qpgpu_solve_batched_dual")
-            return
-        if eq_out is None:
-            rc = LIB.qpgpu_solve_batched(*args, ctypes.c_void_p(stream.cuda_stream))
-        else:
-            rc = LIB.qpgpu_solve_batched_eq(*args, *[vp(t) for t in eq_out],
-                                            ctypes.c_void_p(stream.cuda_stream))
-        _check(rc, "qpgpu_solve_batched")
+        entry = self._ENTRY if dual_out is None else self._ENTRY_DUAL
+        _, args = self._args(stream, max_iter, flags, dual_out or ())
+        _check(getattr(LIB, entry)(*args), entry)
 
-    def launcher(self, stream, max_iter: int = 0, family=None, exact: bool = False, fast: bool = False):
-        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
-        argument prebuilt (for tight launch loops: ~2 us of host time per launch)."""
-        d = ProblemDesc(self.n, self.p, self.m, max_iter, self.batch,
-                        FAMILY_FLAGS[family] | (FLAG_EXACT if exact else 0) | (FLAG_FAST if fast else 0),
-                        self.layout)
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        args = (ctypes.byref(d), vp(self.G), vp(self.g0), vp(self.CE), vp(self.ce0), vp(self.CI),
-                vp(self.ci0), vp(self.x), vp(self.f), vp(self.status), vp(self.iters),
-                ctypes.c_void_p(stream.cuda_stream))
-        fn = LIB.qpgpu_solve_batched
+    def _launcher(self, stream, max_iter, flags):
+        d, args = self._args(stream, max_iter, flags)
+        fn, entry = getattr(LIB, self._ENTRY), self._ENTRY
 
         def launch():
             rc = fn(*args)
             if rc != SUCCESS:
-                _check(rc, "qpgpu_solve_batched")
+                _check(rc, entry)
 
         launch._keep = (d, self)
         return launch
@@ -518,22 +502,82 @@ class DeviceBatch:
         return x, self.f.cpu().numpy(), self.status.cpu().numpy(), it
 
 
-def solve_batched_dual(pr: Problems, family=None, layout=None, max_iter: int = 0,
-                       write_factor: bool = False, device="cuda:0"):
-    """Solve every QP of `pr` on the GPU and return the multipliers too:
-    (x, f, status, iters, u, nact) as numpy, u of shape (B, p + m) in QP-major order whatever
-    the device layout — u[:, :p] the equalities', u[:, p:] the inequalities' (include/qpgpu.h,
-    qpgpu_solve_batched_dual).  Stages `pr` through device tensors; with write_factor=True,
-    pr.G receives each QP's Cholesky factor."""
+class DeviceBatch(_DeviceBatchBase):
+    """Device-resident inputs/outputs for repeated solves (torch tensors on one GPU)."""
+
+    _INPUTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
+    _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched", "qpgpu_solve_batched_dual"
+
+    def __init__(self, pr: Problems, device, with_iters: bool = True, layout=None):
+        super().__init__(pr, device, with_iters, layout)
+
+    def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
+              eq_out=None, exact: bool = False, fast: bool = False, dual_out=None):
+        """Enqueue one batched solve on `stream` (a torch.cuda.Stream, default current).
+        eq_out=(x_eq, f_eq, status_eq) tensors also receive the m = 0 answer
+        (qpgpu_solve_batched_eq).  dual_out=(u, nact) tensors receive the multipliers, p + m
+        float64 per QP in this batch's layout, and the int32 active-inequality counts
+        (qpgpu_solve_batched_dual: reference operation order always; either may be None where
+        the C entry takes NULL).  eq_out and dual_out are separate entries: not both."""
+        flags = ((FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family]
+                 | (FLAG_EXACT if exact else 0) | (FLAG_FAST if fast else 0))
+        if eq_out is None:
+            return self._solve(stream, max_iter, flags, dual_out)
+        if dual_out is not None:
+            raise ValueError("eq_out and dual_out are separate entry points: pass one")
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(self.x.device)
+        _, args = self._args(stream, max_iter, flags, eq_out)
+        _check(LIB.qpgpu_solve_batched_eq(*args), "qpgpu_solve_batched")
+
+    def launcher(self, stream, max_iter: int = 0, family=None, exact: bool = False, fast: bool = False):
+        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
+        argument prebuilt (for tight launch loops: ~2 us of host time per launch)."""
+        return self._launcher(stream, max_iter,
+                              FAMILY_FLAGS[family] | (FLAG_EXACT if exact else 0) | (FLAG_FAST if fast else 0))
+
+
+class DeviceBoxBatch(_DeviceBatchBase):
+    """DeviceBatch for bound-constrained QPs (qpgpu_solve_batched_box): hi and lo, n float64 per
+    QP in the layout of x, instead of CI and ci0."""
+
+    _INPUTS = ("G", "g0", "CE", "ce0", "hi", "lo")
+    _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched_box", "qpgpu_solve_batched_box_dual"
+
+    def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
+        super().__init__(bp, device, with_iters, layout)
+
+    def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
+              flags: int = 0, dual_out=None):
+        """Enqueue one batched box solve on `stream` (a torch.cuda.Stream, default current);
+        `flags` are OR-ed in as given (tests pass QPGPU_FLAG_FAST to see it refused).
+        dual_out=(u, nact) tensors receive the multipliers, p + 2n float64 per QP in the layout of
+        x, and the active-set sizes, int32 (qpgpu_solve_batched_box_dual; either may be None where
+        the C entry takes NULL)."""
+        self._solve(stream, max_iter, (FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family] | flags,
+                    dual_out)
+
+    def launcher(self, stream, max_iter: int = 0, family=None):
+        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
+        argument prebuilt (see DeviceBatch.launcher)."""
+        return self._launcher(stream, max_iter, FAMILY_FLAGS[family])
+
+
+def _solve_with_multipliers(db, pr, family, max_iter, write_factor):
+    """The staging and unpacking solve_batched_dual and solve_batched_box_dual share: u and nact
+    tensors for `db` (the device batch of `pr`), the solve, and every result as numpy in QP-major
+    order; with write_factor, pr.G receives the factors."""
     import torch
 
-    db = DeviceBatch(pr, device, layout=layout)
+    device = db.x.device
     B, E = pr.batch, pr.p + pr.m
     rows = (B + 63) // 64 * 64 if db.layout == LAYOUT_TILED64 else B
     u = torch.zeros((rows, E), dtype=torch.float64, device=device)
     nact = torch.zeros(B, dtype=torch.int32, device=device)
     db.solve(max_iter=max_iter, write_factor=write_factor, family=family, dual_out=(u, nact))
-    torch.cuda.synchronize(db.x.device)
+    torch.cuda.synchronize(device)
     x, f, st, it = db.results()
     uh = u.cpu().numpy()
     if db.layout == LAYOUT_TILED64:
@@ -544,72 +588,14 @@ def solve_batched_dual(pr: Problems, family=None, layout=None, max_iter: int = 0
     return x, f, st, it, uh.reshape(B, E), nact.cpu().numpy()
 
 
-class DeviceBoxBatch:
-    """DeviceBatch for bound-constrained QPs (qpgpu_solve_batched_box): hi and lo, n float64 per
-    QP in the layout of x, instead of CI and ci0."""
-
-    def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
-        import torch
-
-        self.n, self.p, self.m, self.batch = bp.n, bp.p, 2 * bp.n, bp.batch
-        self.layout = LAYOUTS[layout]
-        conv = to_tiled64 if self.layout == LAYOUT_TILED64 else (lambda a: a)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(conv(np.asarray(a, dtype=np.float64)))).to(device)
-        self.G, self.g0, self.CE, self.ce0, self.hi, self.lo = (t(a) for a in bp.arrays())
-        rows = (self.batch + 63) // 64 * 64 if self.layout == LAYOUT_TILED64 else self.batch
-        self.x = torch.zeros((rows, self.n), dtype=torch.float64, device=device)
-        self.f = torch.zeros(self.batch, dtype=torch.float64, device=device)
-        self.status = torch.zeros(self.batch, dtype=torch.int32, device=device)
-        self.iters = torch.zeros(self.batch, dtype=torch.int32, device=device) if with_iters else None
-
-    def _args(self, stream, max_iter, flags):
-        d = ProblemDesc(self.n, self.p, self.m, max_iter, self.batch, flags, self.layout)
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        return d, (ctypes.byref(d), vp(self.G), vp(self.g0), vp(self.CE), vp(self.ce0), vp(self.hi),
-                   vp(self.lo), vp(self.x), vp(self.f), vp(self.status), vp(self.iters),
-                   ctypes.c_void_p(stream.cuda_stream))
-
-    def solve(self, stream=None, max_iter: int = 0, write_factor: bool = False, family=None,
-              flags: int = 0, dual_out=None):
-        """Enqueue one batched box solve on `stream` (a torch.cuda.Stream, default current);
-        `flags` are OR-ed in as given (tests pass QPGPU_FLAG_FAST to see it refused).
-        dual_out=(u, nact) tensors receive the multipliers, p + 2n float64 per QP in the layout of
-        x, and the active-set sizes, int32 (qpgpu_solve_batched_box_dual; either may be None where
-        the C entry takes NULL)."""
-        import torch
-
-        if stream is None:
-            stream = torch.cuda.current_stream(self.x.device)
-        _, args = self._args(stream, max_iter,
-                             (FLAG_WRITE_FACTOR if write_factor else 0) | FAMILY_FLAGS[family] | flags)
-        if dual_out is not None:
-            u, nact = dual_out
-            vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            rc = LIB.qpgpu_solve_batched_box_dual(*args[:-1], vp(u), vp(nact), args[-1])
-            _check(rc, "qpgpu_solve_batched_box_dual")
-            return
-        _check(LIB.qpgpu_solve_batched_box(*args), "qpgpu_solve_batched_box")
-
-    def launcher(self, stream, max_iter: int = 0, family=None):
-        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
-        argument prebuilt (see DeviceBatch.launcher)."""
-        d, args = self._args(stream, max_iter, FAMILY_FLAGS[family])
-        fn = LIB.qpgpu_solve_batched_box
-
-        def launch():
-            rc = fn(*args)
-            if rc != SUCCESS:
-                _check(rc, "qpgpu_solve_batched_box")
-
-        launch._keep = (d, self)
-        return launch
-
-    def results(self):
-        it = None if self.iters is None else self.iters.cpu().numpy()
-        x = self.x.cpu().numpy()
-        if self.layout == LAYOUT_TILED64:
-            x = from_tiled64(x.reshape(-1), self.batch, (self.n,))
-        return x, self.f.cpu().numpy(), self.status.cpu().numpy(), it
+def solve_batched_dual(pr: Problems, family=None, layout=None, max_iter: int = 0,
+                       write_factor: bool = False, device="cuda:0"):
+    """Solve every QP of `pr` on the GPU and return the multipliers too:
+    (x, f, status, iters, u, nact) as numpy, u of shape (B, p + m) in QP-major order whatever
+    the device layout — u[:, :p] the equalities', u[:, p:] the inequalities' (include/qpgpu.h,
+    qpgpu_solve_batched_dual).  Stages `pr` through device tensors; with write_factor=True,
+    pr.G receives each QP's Cholesky factor."""
+    return _solve_with_multipliers(DeviceBatch(pr, device, layout=layout), pr, family, max_iter, write_factor)
 
 
 def solve_batched_box(bp: BoxProblems, family=None, layout=None, max_iter: int = 0, device="cuda:0"):
@@ -629,23 +615,7 @@ def solve_batched_box_dual(bp: BoxProblems, family=None, layout=None, max_iter: 
     (x, f, status, iters, u, nact) as numpy, u of shape (B, p + 2n) in QP-major order whatever the
     device layout — u[:, :p] the equalities', u[:, p:p+n] the upper bounds', u[:, p+n:] the lower
     bounds' (include/qpgpu.h).  With write_factor=True, bp.G receives each QP's Cholesky factor."""
-    import torch
-
-    db = DeviceBoxBatch(bp, device, layout=layout)
-    B, E = bp.batch, bp.p + 2 * bp.n
-    rows = (B + 63) // 64 * 64 if db.layout == LAYOUT_TILED64 else B
-    u = torch.zeros((rows, E), dtype=torch.float64, device=device)
-    nact = torch.zeros(B, dtype=torch.int32, device=device)
-    db.solve(max_iter=max_iter, write_factor=write_factor, family=family, dual_out=(u, nact))
-    torch.cuda.synchronize(db.x.device)
-    x, f, st, it = db.results()
-    uh = u.cpu().numpy()
-    if db.layout == LAYOUT_TILED64:
-        uh = from_tiled64(uh.reshape(-1), B, (E,))
-    if write_factor:
-        Gh = db.G.cpu().numpy()
-        bp.G[...] = from_tiled64(Gh.reshape(-1), B, (bp.n, bp.n)) if db.layout == LAYOUT_TILED64 else Gh
-    return x, f, st, it, uh.reshape(B, E), nact.cpu().numpy()
+    return _solve_with_multipliers(DeviceBoxBatch(bp, device, layout=layout), bp, family, max_iter, write_factor)
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):
