@@ -303,7 +303,77 @@ int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d,
  * (every such name contains "box" and "dual"); "" where qpgpu_kernel_name_box returns "". */
 const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags);
 
-/* Same, with HOST pointers: copies the inputs to the device, solves, copies the outputs back
+/* ---- the KKT check: is (x, u) a solution of its QP? ---------------------------------------------
+ * qpgpu_kkt_residuals evaluates, on the device, the optimality conditions of every QP of a batch
+ * at a given primal-dual pair: QPGPU_KKT_NRES doubles per QP, independent of any reference solver.
+ * It is the caller's means to detect multipliers that miss the identities at
+ * qpgpu_solve_batched_dual (the rollback quirk) and to certify an x of the 1e-10 modes.
+ *
+ * Device pointers, enqueue only.  No workspace for any shape: the first call for a shape can be
+ * captured into a hipGraph.  Inputs are laid out exactly as qpgpu_solve_batched_dual takes and
+ * produces them (u: p + m doubles per QP), in either layout; r is QPGPU_KKT_NRES doubles per QP in
+ * the layout of x (QP-major: r + b*8 + k; TILED64: a per-QP block of E = 8).  Natural alignment and
+ * sub-ranges as at the top of this file; the call writes the r blocks of its own QPs and nothing
+ * else (no TILED64 padding slot, no input).  Every shape the solve entries accept (n >= 1, n*n and
+ * n*m below 2^31; beyond: QPGPU_ERR_UNSUPPORTED_SHAPE).  d->max_iter is ignored; d->flags must be 0.
+ * Decided before any array is read, QPGPU_ERR_INVALID_ARGUMENT: non-zero flags; a NULL u with
+ * p + m > 0; with batch > 0 a NULL G, g0, x or r, a NULL CE / ce0 with p > 0, a NULL CI / ci0 with
+ * m > 0.  batch = 0 is QPGPU_SUCCESS.  status may be NULL: every QP is evaluated.  With status
+ * given, a QP whose status is not QPGPU_QP_OK gets all eight slots NaN (its x is not meaningful,
+ * and was never written for QPGPU_QP_NOT_POSITIVE_DEFINITE).
+ *
+ * The definition, which the kernel reproduces bit for bit (tests/kkt_ref.py restates it).
+ * ue = u[0:p], ui = u[p:]; |.| is fabs; every sum starts from +0.0 and adds in ascending index;
+ * every product is rounded before it is added (no FMA); every division is IEEE;
+ *     ratio(a, b) = b > 0 ? a / b : a
+ *     smax(acc, v) = acc is NaN ? acc : ((v > acc || v != v) ? v : acc)
+ * and every running maximum uses smax from +0.0, so a NaN anywhere is kept.  G is read as stored,
+ * row by row: the check assumes the symmetric G the solver assumes.
+ *   for each row i < n:
+ *     a_i  = sum_j G[i][j] x[j]             aa_i = sum_j |G[i][j]| |x[j]|
+ *     c_i  = sum_k<p CE[i][k] ue[k]         ca_i = sum_k |CE[i][k]| |ue[k]|
+ *     d_i  = sum_k<m CI[i][k] ui[k]         da_i = sum_k |CI[i][k]| |ui[k]|
+ *     t_i  = ((a_i + g0[i]) - c_i) - d_i    ts_i = ((aa_i + |g0[i]|) + ca_i) + da_i
+ *     stat = smax_i |t_i|     scale = smax_i ts_i     q = sum_i x[i] a_i     l = sum_i g0[i] x[i]
+ *   for each equality k < p:    e_k = (sum_i CE[i][k] x[i]) + ce0[k]   ea_k = (sum_i |CE[i][k]| |x[i]|) + |ce0[k]|
+ *   for each inequality k < m:  s_k = (sum_i CI[i][k] x[i]) + ci0[k]   sa_k = (sum_i |CI[i][k]| |x[i]|) + |ci0[k]|
+ *   r[QPGPU_KKT_STAT]       = ratio(stat, scale)    scaled stationarity residual of G x + g0 = CE ue + CI ui
+ *   r[QPGPU_KKT_STAT_SCALE] = scale
+ *   r[QPGPU_KKT_EQ]         = smax_k ratio(|e_k|, ea_k)
+ *   r[QPGPU_KKT_INEQ]       = smax_k ( s_k < 0 ? ratio(-s_k, sa_k) : (s_k != s_k ? NaN : 0.0) )
+ *   r[QPGPU_KKT_COMP]       = smax over k with ui[k] != 0 of ratio(|s_k|, sa_k)
+ *   r[QPGPU_KKT_UMIN]       = the smallest ui[k] that is < 0, else +0.0  (running v < acc ? v : acc from +0.0)
+ *   r[QPGPU_KKT_OBJ]        = 0.5 q + l
+ *   r[QPGPU_KKT_NNZ]        = the number of k with ui[k] != 0, as a double
+ * Slots STAT, EQ, INEQ and COMP are residuals over the magnitude of their own terms: a solution in
+ * binary64 leaves them at a small multiple of 2^-53 at every scaling of the problem.  A bound
+ * ci0[k] = +inf gives s_k = +inf: no violation and, with ui[k] == 0, no complementarity term. */
+#define QPGPU_KKT_NRES 8
+enum { QPGPU_KKT_STAT, QPGPU_KKT_STAT_SCALE, QPGPU_KKT_EQ, QPGPU_KKT_INEQ,
+       QPGPU_KKT_COMP, QPGPU_KKT_UMIN, QPGPU_KKT_OBJ, QPGPU_KKT_NNZ };
+
+int qpgpu_kkt_residuals(const qpgpu_problem_desc* d,
+                        const double* G, const double* g0, const double* CE, const double* ce0,
+                        const double* CI, const double* ci0,
+                        const double* x, const double* u, const int32_t* status,
+                        double* r, void* stream);
+
+/* The same for bounds lo <= x <= hi, with u in the layout of qpgpu_solve_batched_box_dual.  DEFINED
+ * as qpgpu_kkt_residuals on CI = [-I, +I], ci0 = [hi; -lo] (d->m must be 2 * d->n; NULL hi or lo
+ * with batch > 0 is QPGPU_ERR_INVALID_ARGUMENT) and equal to it bit for bit under the finite-data
+ * condition stated at qpgpu_solve_batched_box: each sum over a row or column of that CI is its one
+ * or two non-zero terms added to the +0.0 it starts from,
+ *     d_i = (0.0 - u[p+i]) + u[p+n+i]            da_i = (0.0 + |u[p+i]|) + |u[p+n+i]|
+ *     s_k = (0.0 - x[k]) + hi[k]                 sa_k = (0.0 + |x[k]|) + |hi[k]|        (k < n)
+ *     s_(n+k) = (0.0 + x[k]) + (-lo[k])          sa_(n+k) = (0.0 + |x[k]|) + |-lo[k]|
+ * The kernel reads no CI. */
+int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d,
+                            const double* G, const double* g0, const double* CE, const double* ce0,
+                            const double* hi, const double* lo,
+                            const double* x, const double* u, const int32_t* status,
+                            double* r, void* stream);
+
+/* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).
  * Each host thread has its own device buffers, pinned staging buffer and stream.

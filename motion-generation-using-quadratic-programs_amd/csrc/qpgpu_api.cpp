@@ -19,6 +19,7 @@
 
 #include "../../include/qpgpu.h"
 #include "qp_common.h"
+#include "qp_kkt.h"
 
 extern "C" int qpk_medium_max_n(void);
 extern "C" int qpk_medium_max_m(void);
@@ -454,6 +455,52 @@ int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d, double* G, const d
   return run(d, a, stream);
 }
 
+
+// ---- the KKT check (include/qpgpu.h; kernel: qp_kkt.hip) -------------------------------
+// Both entries: every rule is decided from the descriptor and the pointers' values, before any
+// array is read; no workspace, one kernel, so the first call for a shape can be captured.
+static int kkt_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* g0,
+                   const double* CE, const double* ce0, const double* CI, const double* ci0,
+                   const double* hi, const double* lo, const double* x, const double* u,
+                   const int32_t* status, double* r, void* stream) {
+  if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
+    return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->flags != 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (box && (int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->p + d->m > 0 && !u) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0) {
+    if (!G || !g0 || !x || !r) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (d->p > 0 && (!CE || !ce0)) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (box ? (!hi || !lo) : (d->m > 0 && (!CI || !ci0))) return QPGPU_ERR_INVALID_ARGUMENT;
+  }
+  // the solve entries' size limit (qp_generic.hip): a per-QP block is indexed with 32 bits
+  const int64_t lim = (int64_t)1 << 31;
+  if ((int64_t)d->n * d->n >= lim || (int64_t)d->n * d->m >= lim || (int64_t)d->n * d->p >= lim ||
+      (int64_t)d->p + d->m >= lim)
+    return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  if (d->batch == 0) return QPGPU_SUCCESS;
+  qpk::KktArgs a = {d->n, d->p, d->m, 0, d->batch, 0, G, g0, CE, ce0, box ? nullptr : CI, box ? nullptr : ci0,
+                    box ? hi : nullptr, box ? lo : nullptr, x, u, status, r};
+  const hipError_t e = qpk_launch_kkt(&a, d->layout == QPGPU_LAYOUT_TILED64, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_kkt_residuals(const qpgpu_problem_desc* d, const double* G, const double* g0,
+                        const double* CE, const double* ce0, const double* CI, const double* ci0,
+                        const double* x, const double* u, const int32_t* status, double* r,
+                        void* stream) {
+  return kkt_run(d, false, G, g0, CE, ce0, CI, ci0, nullptr, nullptr, x, u, status, r, stream);
+}
+
+int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d, const double* G, const double* g0,
+                            const double* CE, const double* ce0, const double* hi, const double* lo,
+                            const double* x, const double* u, const int32_t* status, double* r,
+                            void* stream) {
+  return kkt_run(d, true, G, g0, CE, ce0, nullptr, nullptr, hi, lo, x, u, status, r, stream);
+}
 
 // Host-pointer entry (the drop-in's path, one QP per solve_quadprog() call, and the batched
 // controller's).  Device buffers are one allocation per thread, laid out

@@ -56,6 +56,10 @@ LAYOUT_QP_MAJOR = 0
 LAYOUT_TILED64 = 1
 LAYOUTS = {None: 0, "qp_major": LAYOUT_QP_MAJOR, "tiled64": LAYOUT_TILED64}
 
+# slots of a QP's block of qpgpu_kkt_residuals (include/qpgpu.h)
+KKT_STAT, KKT_STAT_SCALE, KKT_EQ, KKT_INEQ, KKT_COMP, KKT_UMIN, KKT_OBJ, KKT_NNZ = range(8)
+KKT_NRES = 8
+
 EXPORTED_SYMBOLS = (
     "qpgpu_solve_batched",
     "qpgpu_solve_batched_eq",
@@ -64,6 +68,8 @@ EXPORTED_SYMBOLS = (
     "qpgpu_kernel_name_box",
     "qpgpu_solve_batched_box_dual",
     "qpgpu_kernel_name_box_dual",
+    "qpgpu_kkt_residuals",
+    "qpgpu_kkt_residuals_box",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -114,6 +120,10 @@ def _load():
     lib.qpgpu_solve_batched_box_dual.restype = ctypes.c_int
     lib.qpgpu_kernel_name_box_dual.argtypes = [ctypes.c_int32] * 2 + [ctypes.c_uint32]
     lib.qpgpu_kernel_name_box_dual.restype = ctypes.c_char_p
+    lib.qpgpu_kkt_residuals.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
+    lib.qpgpu_kkt_residuals.restype = ctypes.c_int
+    lib.qpgpu_kkt_residuals_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
+    lib.qpgpu_kkt_residuals_box.restype = ctypes.c_int
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -444,10 +454,11 @@ def solve_batched_host(pr: Problems, write_factor: bool = False, max_iter: int =
 class _DeviceBatchBase:
     """What DeviceBatch and DeviceBoxBatch share: the device tensors, the prebuilt ctypes arguments
     and the results.  A subclass names its six input attributes (_INPUTS: the order of its
-    problem container's arrays() and of the C entries' arguments) and its two C entries."""
+    problem container's arrays() and of the C entries' arguments) and its C entries (solve, solve
+    with multipliers, KKT check)."""
 
     _INPUTS = ()
-    _ENTRY = _ENTRY_DUAL = None
+    _ENTRY = _ENTRY_DUAL = _ENTRY_KKT = None
 
     def __init__(self, pr, device, with_iters: bool = True, layout=None):
         import torch
@@ -494,6 +505,36 @@ class _DeviceBatchBase:
         launch._keep = (d, self)
         return launch
 
+    def kkt_residuals(self, u, r=None, status=True, stream=None, x=None):
+        """Enqueue the KKT check (qpgpu_kkt_residuals / _box, include/qpgpu.h) of this batch's
+        resident inputs at (x, u) on `stream` (default current): no host round trip, so it can
+        follow a dual solve on the same stream.  u: p + m float64 per QP in this batch's layout (a
+        dual solve's dual_out[0]; may be None when p + m == 0); x: default this batch's own.
+        status=True masks by this batch's status (a non-OK QP's block is all NaN), None or False
+        evaluates every QP, a tensor is used as given.  Returns r, the (rows, 8) float64 device
+        tensor written (TILED64: tiles of [8][64] as x's; kkt_rows() decodes a host copy)."""
+        import torch
+
+        x = self.x if x is None else x
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        if r is None:
+            r = torch.empty((x.numel() // self.n, KKT_NRES), dtype=torch.float64, device=x.device)
+        st = self.status if status is True else (None if status is None or status is False else status)
+        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        tensors = [getattr(self, k) for k in self._INPUTS] + [x, u, st, r]
+        _check(getattr(LIB, self._ENTRY_KKT)(ctypes.byref(d), *[vp(t) for t in tensors],
+                                             ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_KKT)
+        return r
+
+    def kkt_rows(self, r):
+        """A kkt_residuals() result as numpy (batch, 8), whatever the layout."""
+        rh = r.cpu().numpy()
+        if self.layout == LAYOUT_TILED64:
+            return from_tiled64(rh.reshape(-1), self.batch, (KKT_NRES,))
+        return rh.reshape(-1, KKT_NRES)[:self.batch]
+
     def results(self):
         it = None if self.iters is None else self.iters.cpu().numpy()
         x = self.x.cpu().numpy()
@@ -507,6 +548,7 @@ class DeviceBatch(_DeviceBatchBase):
 
     _INPUTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
     _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched", "qpgpu_solve_batched_dual"
+    _ENTRY_KKT = "qpgpu_kkt_residuals"
 
     def __init__(self, pr: Problems, device, with_iters: bool = True, layout=None):
         super().__init__(pr, device, with_iters, layout)
@@ -545,6 +587,7 @@ class DeviceBoxBatch(_DeviceBatchBase):
 
     _INPUTS = ("G", "g0", "CE", "ce0", "hi", "lo")
     _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched_box", "qpgpu_solve_batched_box_dual"
+    _ENTRY_KKT = "qpgpu_kkt_residuals_box"
 
     def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
         super().__init__(bp, device, with_iters, layout)
@@ -616,6 +659,28 @@ def solve_batched_box_dual(bp: BoxProblems, family=None, layout=None, max_iter: 
     device layout — u[:, :p] the equalities', u[:, p:p+n] the upper bounds', u[:, p+n:] the lower
     bounds' (include/qpgpu.h).  With write_factor=True, bp.G receives each QP's Cholesky factor."""
     return _solve_with_multipliers(DeviceBoxBatch(bp, device, layout=layout), bp, family, max_iter, write_factor)
+
+
+def kkt_residuals(pr, x, u, status=None, layout=None, device="cuda:0"):
+    """The KKT residuals of (x, u) for every QP of `pr` (Problems: qpgpu_kkt_residuals; BoxProblems:
+    qpgpu_kkt_residuals_box), computed on the GPU: a (B, 8) float64 array indexed by KKT_STAT ...
+    KKT_NNZ (include/qpgpu.h).  x is (B, n), u is (B, p + m) in QP-major order (as
+    solve_batched_dual / solve_batched_box_dual return them; may be None when p + m == 0); with
+    `status` (B int32) a QP that is not QP_OK gets an all-NaN row.  layout="tiled64" runs the
+    TILED64 form of the kernel (the arrays are converted here on the host)."""
+    import torch
+
+    db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
+    B, E = pr.batch, pr.p + pr.m
+    conv = to_tiled64 if db.layout == LAYOUT_TILED64 else (lambda a: a)
+    up = lambda a, cols: torch.from_numpy(np.array(
+        conv(np.asarray(a, dtype=np.float64).reshape(B, cols)), dtype=np.float64, order="C")).to(device)
+    xd = up(x, pr.n)
+    ud = up(u, E) if E > 0 else None
+    sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
+    r = db.kkt_residuals(ud, status=sd, x=xd)
+    torch.cuda.synchronize(r.device)
+    return db.kkt_rows(r)
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):
