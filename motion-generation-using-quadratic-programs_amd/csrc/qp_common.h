@@ -439,6 +439,10 @@ hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream);
 // the QPGPU_LANE_UNALIGNED builds of the two, launched when kArgStage16 is not set
 hipError_t qpk_launch_lane_u(const qpk::QpArgs* a, hipStream_t stream);
 hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream);
+// qpgpu_api.cpp, called by the exact aligned build's launcher where a launch splits into its whole
+// 64-QP blocks (full = 1: the full-wave kernel was enqueued) and the remaining QPs (full = 0: the
+// general kernel for them): the counts behind the test hook qpgpu_debug_lane_launches
+void qpk_lane_count_launch(int full);
 const char* qpk_small_name(int n, int m, int mode);  // qp_small.hip
 hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream);
 const char* qpk_medium_name(int n, int m, int mode);       // qp_wave.hip

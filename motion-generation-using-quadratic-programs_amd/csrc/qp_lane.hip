@@ -148,6 +148,12 @@ constexpr int kScanDepth = 2;
 #ifndef QPGPU_LANE_LOOPTOP_EXIT
 #define QPGPU_LANE_LOOPTOP_EXIT 1
 #endif
+// The full-wave aligned kernels (lane_body's FULL; qp_lane_full_kernel) for the whole 64-QP
+// blocks of a C1 / C4 / C2-shaped launch: 1 = the product, 0 = every launch runs the general
+// body (A/B only).
+#ifndef QPGPU_LANE_FULL
+#define QPGPU_LANE_FULL 1
+#endif
 
 // ---- arithmetic of the fast build (frcp, rcp_ok, ldiv_r, ldiv, ldistance): qp_common.h,
 // shared with the lane-pair kernel (qp_pair.hip).
@@ -175,10 +181,20 @@ constexpr int kScanDepth = 2;
 // reduce to their one non-zero term added to the +0.0 the sum starts from: the l1
 // scan is (0.0 -+ x[v]) + b, d = J^T np is 0.0 -+ J[v][:], z.np is 0.0 -+ z[v].  No CI copy in LDS,
 // no DMA staging, no cache warm-up, no CI / ci0 load of any kind.
-template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false, bool BOX = false>
+// FULL (the exact aligned build's EXACT shapes with PX known; qp_lane_full_kernel): the host has
+// established that every wave of the launch is full, that G, g0, CE and ce0 pass the 16-byte
+// staging check (kArgStage16) and CI and ci0 theirs (kArgAligned16), that the factor is not
+// written back and that no pass count is asked for.  live, full, dma, ce_staged, ce_agpr, ci_lds
+// and vec are then constants: the `live ?:` selects, the partial wave's per-lane staging, the
+// LDS and global sources of CE and the scalar CI row loads leave the code, and with them their
+// branches.  The arithmetic is the same operations in the same order.
+template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false, bool BOX = false,
+          bool FULL = false>
 __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   static_assert(MM <= 64, "bitmask bookkeeping holds m <= 64");
   static_assert(!BOX || (!kFast && MM == 2 * NM), "the box mode is the exact build's, m = 2n");
+  static_assert(!FULL || (!kFast && !QPGPU_LANE_UNALIGNED && EXACT && PX >= 0 && !DUAL && !BOX),
+                "the full-wave form is the exact aligned build's, for a compile-time shape");
   static_assert(!DUAL || (!kFast && (BOX || (!EXACT && PX < 0))),
                 "the dual mode is the exact build's general instantiation, or a box form");
   using RI = RIdx<NM>;
@@ -194,7 +210,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   const int64_t b0 = (int64_t)blockIdx.x * kQpw;
   const int64_t b = b0 + lane;
   const int valid = (int)min<int64_t>(kQpw, a.batch - b0);
-  const bool live = lane < valid;
+  const bool live = FULL || lane < valid;
 
   // EXACT: the shape is (NM, *, MM), so every element offset is a compile-time constant
   const int n = EXACT ? NM : a.n;
@@ -214,7 +230,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
 #if QPGPU_LANE_UNALIGNED
   const bool full = false;
 #else
-  const bool full = (T == 64) || (valid == kQpw);
+  const bool full = FULL || (T == 64) || (valid == kQpw);
 #endif
   auto copy_chunk = [&](const double* src, int nd, int off, int k) {  // doubles [k, k+128)
     const int e = k + 2 * lane;
@@ -287,7 +303,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   constexpr bool kCiDma = kCiRows > 0 && (PX > 0 || (PX == 0 && QPGPU_LANE_DMA_P0));
   constexpr int kCeN = PX > 0 ? NM * PX + PX : 1;  // CE (n x p) then ce0 (p)
   [[maybe_unused]] AgprD ceag[kCiDma ? kCeN : 1];
-  const bool dma = kCiDma && (a.flags & kArgAligned16);
+  const bool dma = kCiDma && (FULL || (a.flags & kArgAligned16));
   double Jreg[NM][NM];  // J lives in registers for the whole solve
   bool ce_staged = false;
   bool ce_agpr = false;
@@ -441,7 +457,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         }
       }
     }
-    if ((a.flags & QPGPU_FLAG_WRITE_FACTOR) && live) {
+    if (!FULL && (a.flags & QPGPU_FLAG_WRITE_FACTOR) && live) {
       double* Gw = view(a.G, n * n);
 #pragma unroll
       for (int i = 0; i < NM; i++)
@@ -941,7 +957,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // by the first l1 scan (which every active lane runs, loading those rows into registers
   // anyway).  Later scans then issue only the remaining rows' global loads, and the
   // selected-column gather takes those rows from LDS — no extra global traffic.
-  const bool ci_lds = kCiRows > 0 && (a.flags & kArgAligned16);
+  const bool ci_lds = kCiRows > 0 && (FULL || (a.flags & kArgAligned16));
   bool ci_ready = false;  // wave-uniform: the on-chip copy has been written (or has landed)
   if constexpr (kCiDma) {
     if (dma && (PX == 0 || ce_agpr)) {
@@ -1055,7 +1071,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
             // (checked on the host: kArgAligned16): load them as dwordx4, half the instructions
             // and half the cache-line lookups per row
             constexpr bool VEC = (T == 1) && EXACT && (MM % 2 == 0);
-            const bool vec = VEC && (a.flags & kArgAligned16);
+            const bool vec = VEC && (FULL || (a.flags & kArgAligned16));
             auto ldrow = [&](double* dst, const double* src) {
               if (VEC && vec) {
 #pragma unroll
@@ -1373,7 +1389,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         if (i < n) xb[i * T] = xv[i];
     }
     a.f[b] = fval;
-    if (a.iters) a.iters[b] = iter;
+    if (!FULL && a.iters) a.iters[b] = iter;
     a.status[b] = status;
   }
   if constexpr (DUAL) {
@@ -1423,6 +1439,66 @@ __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
     }
   } else {
     lane_body<NM, MM, T, EXACT, PX, true>(a, sbuf);
+  }
+}
+
+// The full-wave aligned kernels (lane_body's FULL) of the exact aligned build: the shapes behind
+// C1 / C4 (7, 6, 14) and C2 (7, 0, 14), in both layouts.  Kernels of their own, not a branch in the
+// kernels above (which stay the code they were; a branch in the kernel once pushed the N = 8
+// instantiations into scratch, profiles/placement/kernel_regs_branch_in_kernel.txt).
+#if QPGPU_LANE_FULL && !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED && !QPGPU_LANE_OCC2
+#define QPK_LANE_HAS_FULL 1
+template <int NM, int MM, int T, int PX>
+__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_full_kernel(const QpArgs a) {
+  __shared__ double sbuf[kStage];
+  lane_body<NM, MM, T, true, PX, true, false, false, true>(a, sbuf);
+}
+// Does the full-wave kernel exist for this instantiation, and has the host established what it
+// assumes of the launch (apart from the whole waves, which launch_full_then_rest provides)?
+template <int NM, int MM>
+static bool full_wave_launch(const QpArgs& a) {
+  constexpr uint32_t kAligned = kArgStage16 | kArgAligned16;
+  return NM == 7 && MM == 14 && (a.flags & kAligned) == kAligned && !(a.flags & QPGPU_FLAG_WRITE_FACTOR) &&
+         !a.iters;
+}
+#else
+#define QPK_LANE_HAS_FULL 0
+template <int NM, int MM>
+static bool full_wave_launch(const QpArgs&) {
+  return false;
+}
+#endif
+// The whole 64-QP blocks of the batch through `full`, the remaining QPs (batch % 64) through
+// `rest` as a second launch on the same stream with every per-QP pointer advanced past those
+// blocks.  A whole number of 64-QP blocks is a whole number of tiles and of 512-byte steps, so
+// the remainder's arrays keep the layout and the 16-byte residues the host checked.
+template <class Full, class Rest>
+static void launch_full_then_rest(const QpArgs& a, Full&& full, Rest&& rest) {
+  const int64_t nb = a.batch / kQpw, done = nb * kQpw;
+  if (nb > 0) {
+    QpArgs c = a;
+    c.batch = done;
+    full(c, dim3((unsigned)nb));
+    qpk_lane_count_launch(1);
+  }
+  if (a.batch > done) {
+    const int64_t n = a.n, p = a.p, m = a.m;
+    const auto blocks = [&](auto* q, int64_t E) { return q ? q + done * E : q; };
+    const auto each = [&](auto* q) { return q ? q + done : q; };
+    QpArgs c = a;
+    c.batch = a.batch - done;
+    c.G = blocks(a.G, n * n);
+    c.g0 = blocks(a.g0, n);
+    c.CE = blocks(a.CE, n * p);
+    c.ce0 = blocks(a.ce0, p);
+    c.CI = blocks(a.CI, n * m);
+    c.ci0 = blocks(a.ci0, m);
+    c.x = blocks(a.x, n);
+    c.f = each(a.f);
+    c.status = each(a.status);
+    c.stamps = a.stamps ? a.stamps + nb * kStampSlots : nullptr;
+    rest(c, dim3(1));
+    qpk_lane_count_launch(0);
   }
 }
 
@@ -1514,6 +1590,20 @@ static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
   return hipErrorInvalidValue;
 #endif
   if (a.n == NM && a.m == MM && !a.x_eq) {
+#if QPK_LANE_HAS_FULL
+    if constexpr (NM == 7 && MM == 14)
+      if (a.p == 6 && full_wave_launch<NM, MM>(a)) {
+        launch_full_then_rest(
+            a,
+            [&](const QpArgs& c, dim3 gc) {
+              hipLaunchKernelGGL((qp_lane_full_kernel<NM, MM, T, 6>), gc, blk, 0, stream, c);
+            },
+            [&](const QpArgs& c, dim3 gc) {
+              hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 6>), gc, blk, 0, stream, c);
+            });
+        return hipSuccess;
+      }
+#endif
     if (a.p == 6)
       hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 6>), g, blk, 0, stream, a);
     else if (a.p == 0)
@@ -1537,6 +1627,20 @@ static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream) {
 #else
 template <int NM, int MM, int T>
 static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream) {
+#if QPK_LANE_HAS_FULL
+  if constexpr (NM == 7 && MM == 14)
+    if (full_wave_launch<NM, MM>(a)) {
+      launch_full_then_rest(
+          a,
+          [&](const QpArgs& c, dim3 gc) {
+            hipLaunchKernelGGL((qp_lane_full_kernel<NM, MM, T, 0>), gc, dim3(64), 0, stream, c);
+          },
+          [&](const QpArgs& c, dim3 gc) {
+            hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 0>), gc, dim3(64), 0, stream, c);
+          });
+      return hipSuccess;
+    }
+#endif
   const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
   hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 0>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
   return hipSuccess;

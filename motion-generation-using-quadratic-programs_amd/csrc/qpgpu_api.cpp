@@ -842,6 +842,18 @@ int qpgpu_debug_alignment_bits(const void* G, const void* g0, const void* CE, co
   return ((f & qpk::kArgAligned16) ? 1 : 0) | ((f & qpk::kArgStage16) ? 2 : 0);
 }
 
+// Test hook (not in include/qpgpu.h): how many full-wave lane kernels (out[0]) and how many general
+// lane kernels for the QPs past the last whole 64-QP block (out[1]) this thread's solves have
+// enqueued since the last reset.  A launch that the full-wave kernels do not take — arrays off
+// the 16-byte checks, QPGPU_FLAG_WRITE_FACTOR, a pass count asked for — counts in neither.
+static thread_local int64_t g_lane_launches[2] = {0, 0};
+void qpk_lane_count_launch(int full) { g_lane_launches[full ? 0 : 1]++; }
+void qpgpu_debug_lane_launches(int64_t* out, int reset) {
+  out[0] = g_lane_launches[0];
+  out[1] = g_lane_launches[1];
+  if (reset) g_lane_launches[0] = g_lane_launches[1] = 0;
+}
+
 int qpgpu_relayout(int64_t batch, int32_t elems, const double* src, double* dst, int32_t to_tiled,
                    void* stream) {
   if (batch < 0 || elems < 0 || (batch > 0 && elems > 0 && (!src || !dst)))

@@ -1,7 +1,9 @@
 """Diagnostic: per-phase s_memtime stamps of the lane kernel (qpgpu_debug_set_stamps).
 
 Runs the bench workload once with stamps on and prints, per phase, cycles per wave
-(mean / p50 / p90 / max) plus the wave's l1-pass maximum.  Never used for timing numbers."""
+(mean / p50 / p90 / max) plus the wave's l1-pass maximum.  Never used for timing numbers.
+STAMPS_ITERS=0 stamps launches that ask for no pass count, as bench.py's do (the lane family's
+full-wave kernels take only those); the pass counts then come from a second, unstamped solve."""
 import ctypes
 import os
 import sys
@@ -22,7 +24,8 @@ if kind == "box":
     p = 0
 B = int(os.environ.get("STAMPS_B", "65536"))  # e.g. 1: one QP (BASELINE config 1 latency)
 pr = qpgpu.make_problems(kind, n, p, m, 0, B, seed=2026)
-db = qpgpu.DeviceBatch(pr, "cuda:0", layout=layout)
+with_iters = os.environ.get("STAMPS_ITERS", "1") != "0"
+db = qpgpu.DeviceBatch(pr, "cuda:0", with_iters=with_iters, layout=layout)
 waves = (B + QPW - 1) // QPW
 st = torch.zeros(waves * 18, dtype=torch.int64, device="cuda:0")
 fn = qpgpu.LIB.qpgpu_debug_set_stamps
@@ -33,7 +36,11 @@ for rep in range(3):
     torch.cuda.synchronize()
 fn(None)
 s = st.cpu().numpy().reshape(waves, 18).astype(np.int64)
-itv = db.iters.cpu().numpy()
+if not with_iters:
+    dbi = qpgpu.DeviceBatch(pr, "cuda:0", layout=layout)
+    dbi.solve(family=family, fast=fast)
+    torch.cuda.synchronize()
+itv = (db if with_iters else dbi).iters.cpu().numpy()
 it = np.pad(itv, (0, max(0, waves * QPW - len(itv))))[: waves * QPW].reshape(waves, QPW)
 names = ["loads+setup", "equality", "active-set", "stores"]
 tot = s[:, 4] - s[:, 0]
