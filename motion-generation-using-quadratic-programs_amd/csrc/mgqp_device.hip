@@ -547,6 +547,7 @@ struct CycleWs {
   void* buf = nullptr;
   int64_t qp_count = -1;  // G / g0 initialised for this (count, dim)
   int qp_dim = -1;
+  size_t qp_off = 0;  // ... at this workspace offset (g0 follows G at a distance count and dim fix)
   int lim_m = -1, lim_n = -1;  // the constant limits matrix [-I; +I] uploaded for this (m, n)
   size_t lim_off = 0;          // ... at this workspace offset
 };
@@ -629,10 +630,14 @@ int run_cycle(const Plan& P, int64_t K, const float* Bcumul_host, float* torques
     g_cws.lim_n = n;
     g_cws.lim_off = oB;
   }
-  const bool init_qp = !(g_cws.qp_count == K && g_cws.qp_dim == n);
+  // The solver leaves G = I and g0 = 0 as they are, so they are written once per (count, dim) and
+  // place: the arrays in front of them grow with the task stack's rows, so another stack of the
+  // same count and dim has them elsewhere, over what the last cycle left there.
+  const bool init_qp = !(g_cws.qp_count == K && g_cws.qp_dim == n && g_cws.qp_off == oG);
   if (launch_init(P, W, init_qp ? G : nullptr, g0, s)) return fail("init", hipGetLastError(), err);
   g_cws.qp_count = K;
   g_cws.qp_dim = n;
+  g_cws.qp_off = oG;
   if (launch_build_tasks(P, W, s)) return fail("build_tasks", hipGetLastError(), err);
 
   int last = -1;

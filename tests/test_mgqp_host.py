@@ -171,3 +171,51 @@ def test_cpu_dependent_equalities_raise(harness):
 
 def test_cpu_joint_space_levels(harness):
     G.test_joint_space_levels(None, lib=harness)
+
+
+# --- the shape cases (tests/mgqp_cases.py): every DOF class and stack depth ---------------------
+import mgqp_cases as mc
+import test_gpu_mgqp_shapes as GS
+
+
+@pytest.mark.parametrize("name", sorted(mc.CASES))
+def test_case_plan_reaches_its_kernel(name):
+    """The Python restatement of update_device's row grouping gives the table's stacked rows."""
+    dim, rows, stacked = mc.plan_of(name)
+    assert (dim, stacked) == mc.EXPECTED[name]
+    assert dim <= 2 * mgqp.MAX_DOF
+
+
+def test_case_plans_cover_the_device_code():
+    """Together the device cases reach every register builder, the generic builder, every
+    finish_level_reg<14, R> that the default stacks leave out, and the LDS projector with fewer
+    stacked rows than columns, as many, and more; DOF 1 and 2 have more level-0 rows than columns."""
+    plans = [mc.plan_of(n) for n in GS.DEVICE_CASES]
+    dims = {d for d, _, _ in plans}
+    assert set(mc.REG_BUILDER_DIMS) <= dims and {16, 32} <= dims
+    assert {7, 8, 9, 12} <= {r for d, _, st in plans if d == 14 for r in st}
+    lds = [(d, r) for d, _, st in plans for r in st if not (d == 14 and r in mc.REG_PROJECTOR_ROWS)]
+    assert any(r < d for d, r in lds) and any(r == d for d, r in lds) and any(r > d for d, r in lds)
+    for name in ("dof1", "dof2"):
+        dim, rows, _ = mc.plan_of(name)
+        assert rows[0] > dim
+    assert set(GS.DEVICE_CASES) | {"dof1", "dof2", "dof8_default"} == set(mc.CASES)
+
+
+@pytest.mark.parametrize("name,K,seed", GS.ORACLE_CASES)
+def test_cpu_host_matches_oracle_shapes(harness, name, K, seed):
+    GS.test_host_matches_oracle(None, name, K, seed, lib=harness)
+
+
+@pytest.mark.parametrize("name", GS.BITWISE_CASES)
+def test_cpu_batched_equals_single_bitwise_shapes(harness, name):
+    GS.test_batched_equals_single_bitwise(None, name, lib=harness)
+
+
+def test_cpu_narrow_jacobian_zero_fill(harness):
+    GS.test_narrow_jacobian_zero_fill(None, lib=harness)
+
+
+@pytest.mark.parametrize("name", ["dof1", "dof2"])
+def test_cpu_more_rows_than_columns_raise(harness, name):
+    GS.test_more_rows_than_columns_raise(None, name, lib=harness)
