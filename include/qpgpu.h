@@ -373,6 +373,87 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d,
                             const double* x, const double* u, const int32_t* status,
                             double* r, void* stream);
 
+/* ---- the backward step: gradients of the solution with respect to the data ------------------------
+ * qpgpu_vjp evaluates, on the device, the vector-Jacobian product of every QP of a batch: given
+ * gx = dl/dx at the solution x* of
+ *     min 0.5 x^T G x + g0^T x   s.t.  CE^T x + ce0 = 0,  CI^T x + ci0 >= 0,
+ * the gradients of l with respect to G, g0, CE, ce0, CI and ci0.  With A = [CE, CI_act] the n x q
+ * matrix of working columns, lam their multipliers and b their offsets, the solution satisfies
+ * G x + g0 = A lam and A^T x + b = 0; solving  G a + A c = gx,  A^T a = 0  gives
+ *     dg0 = -a,   dG = -1/2 (a x^T + x a^T),   dA = a lam^T - x c^T,   db = -c.
+ * dG is the gradient with respect to a SYMMETRIC G, the G the solver assumes (only its lower
+ * triangle is read).  A constraint whose multiplier is exactly 0 is treated as inactive: x* is not
+ * differentiable where a constraint is weakly active, and this is the one-sided choice made there.
+ * Gradients of f or of the multipliers are not provided.
+ *
+ * Device pointers, enqueue only.  No workspace for any supported shape: the first call for a shape
+ * can be captured into a hipGraph.  G, CE, CI, x, u and status are laid out exactly as
+ * qpgpu_solve_batched_dual takes and produces them (u: p + m doubles per QP), in either layout; gx
+ * is n doubles per QP in the layout of x; every output has the layout and the per-QP size of the
+ * input it is the gradient of.  Any output pointer may be NULL: that gradient is then neither
+ * computed nor written.  Natural alignment and sub-ranges as at the top of this file; the call
+ * writes the requested gradient blocks of its own QPs and nothing else (no TILED64 padding slot, no
+ * input).
+ *
+ * Shapes: n <= 64 with any p and any m (n*n, n*p and n*m below 2^31).  n > 64 is
+ * QPGPU_ERR_UNSUPPORTED_SHAPE (it needs a workspace or a blocked factorisation).  d->max_iter is
+ * ignored; d->flags must be 0.  Decided before any array is read, QPGPU_ERR_INVALID_ARGUMENT:
+ * non-zero flags; a NULL u with p + m > 0; with batch > 0 a NULL G, x or gx, a NULL CE with p > 0, a
+ * NULL CI with m > 0.  batch = 0 is QPGPU_SUCCESS.  status may be NULL: every QP is evaluated.  With
+ * status given, a QP whose status is not QPGPU_QP_OK gets +0.0 in every requested output: no
+ * gradient flows through a failed QP.
+ *
+ * The definition, which the kernels reproduce bit for bit (tests/vjp_ref.py restates it).  No FMA:
+ * every product is rounded before it is added or subtracted; division and sqrt are IEEE; there is
+ * no branch on any pivot: a non-positive pivot yields NaN or inf by IEEE rules and propagates.
+ *   Working list W: the equalities k = 0..p-1 in order, then the inequalities i in ascending order
+ *   with u[p+i] != 0.  q = |W|; col(t) is the CE or CI column at position t, lam(t) its u entry.
+ *   If q > n, every requested output element of the QP is NaN.
+ *   chol(A), reads the lower triangle only; for j ascending:
+ *       s = A[j][j]; for k < j ascending s = s - L[j][k]*L[j][k];  L[j][j] = sqrt(s)
+ *       for i > j:  s = A[i][j]; for k < j ascending s = s - L[i][k]*L[j][k];  L[i][j] = s / L[j][j]
+ *   fsub(L, r), for i ascending:   s = r[i]; for k < i ascending s = s - L[i][k]*y[k];  y[i] = s / L[i][i]
+ *   bsub(L, r) solves L^T z = r, for i descending (N the order of L):
+ *       s = r[i]; for k = i+1..N-1 ascending s = s - L[k][i]*z[k];  z[i] = s / L[i][i]
+ *   L = chol(G);  w = fsub(L, gx);  M[:,t] = fsub(L, col(t)) for t < q
+ *   S[s][t] = sum_i M[i][s]*M[i][t] for s >= t,  r[t] = sum_i M[i][t]*w[i]   (from +0.0, i ascending)
+ *   R = chol(S);  c = bsub(R, fsub(R, r))
+ *   y[i] = w[i], then for t ascending y[i] = y[i] - M[i][t]*c[t];  a = bsub(L, y)
+ *   dg0[i]    = -a[i]
+ *   dG[i][j]  = -0.5 * (a[i]*x[j] + x[i]*a[j])                  (bit-symmetric)
+ *   dCE[i][k] = a[i]*u[k] - x[i]*c[k]        dce0[k] = -c[k]
+ *   inequality j at position t of W:  dCI[i][j] = a[i]*u[p+j] - x[i]*c[t],  dci0[j] = -c[t]
+ *   inequality j not in W:            dCI[i][j] = +0.0,                      dci0[j] = +0.0
+ * The Goldfarb-Idnani working set has independent columns, so q <= n and S is positive definite
+ * on every pair (x, u) the dual solve entries produce with QPGPU_QP_OK. */
+int qpgpu_vjp(const qpgpu_problem_desc* d,
+              const double* G, const double* CE, const double* CI,
+              const double* x, const double* u, const int32_t* status,
+              const double* gx,
+              double* dG, double* dg0, double* dCE, double* dce0, double* dCI, double* dci0,
+              void* stream);
+
+/* The same for bounds lo <= x <= hi, with u in the layout of qpgpu_solve_batched_box_dual (d->m must
+ * be 2 * d->n: anything else is QPGPU_ERR_INVALID_ARGUMENT).  DEFINED as qpgpu_vjp on CI = [-I, +I]
+ * (column k < n: -1.0 at row k among -0.0; column n + k: +1.0 at row k among +0.0, the matrix
+ * BoxProblems.to_dense() of the Python mirror materialises) and equal to it bit for bit; the kernel
+ * generates those columns, reads no CI and writes no dCI.  dhi and dlo are n doubles per QP in the
+ * layout of x:
+ *     dhi[k] = -c[t] if the upper bound of k is at position t of W (u[p+k] != 0),    else +0.0
+ *     dlo[k] = +c[t] if the lower bound of k is at position t of W (u[p+n+k] != 0),  else +0.0
+ * (ci0 = [hi; -lo], so dhi = dci0[0:n] and dlo = -dci0[n:2n] on the active bounds). */
+int qpgpu_vjp_box(const qpgpu_problem_desc* d,
+                  const double* G, const double* CE,
+                  const double* x, const double* u, const int32_t* status,
+                  const double* gx,
+                  double* dG, double* dg0, double* dCE, double* dce0, double* dhi, double* dlo,
+                  void* stream);
+
+/* Name of the kernel a qpgpu_vjp / qpgpu_vjp_box launch of this shape runs: a name containing
+ * "lane" (one QP per lane) for n <= 8, "group" (one QP per 16, 32 or 64 lanes) for 8 < n <= 64,
+ * "" for n > 64 or n <= 0. */
+const char* qpgpu_kernel_name_vjp(int32_t n, int32_t p, int32_t m);
+
 /* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -1,0 +1,38 @@
+// qp_vjp.h — what qp_vjp.hip exports to qpgpu_api.cpp: the argument block of the backward step
+// (include/qpgpu.h qpgpu_vjp / qpgpu_vjp_box), its launch and the name of the kernel it runs.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace qpk {
+
+struct VjpArgs {
+  int n, p, m;
+  int box;             // non-zero: CI = [-I, +I] is generated, never read; dhi / dlo instead of dCI / dci0
+  int64_t batch, qp0;  // a launch covers QPs [qp0, batch); callers pass qp0 = 0
+  const double* G;
+  const double* CE;
+  const double* CI;  // NULL with box
+  const double* x;
+  const double* u;
+  const int32_t* status;  // may be NULL: every QP is evaluated
+  const double* gx;
+  // the gradients; each may be NULL (not computed, not written)
+  double* dG;
+  double* dg0;
+  double* dCE;
+  double* dce0;
+  double* dCI;   // dense only
+  double* dci0;  // dense only
+  double* dhi;   // box only
+  double* dlo;   // box only
+};
+
+}  // namespace qpk
+
+// The kernel a launch of this n runs: NULL for n outside [1, 64].
+extern "C" const char* qpk_vjp_name(int n);
+// Enqueue the backward step of QPs [0, a->batch) on `stream`; tiled != 0: QPGPU_LAYOUT_TILED64.
+// n outside [1, 64] is hipErrorInvalidValue.
+extern "C" hipError_t qpk_launch_vjp(const qpk::VjpArgs* a, int tiled, hipStream_t stream);

@@ -20,6 +20,7 @@
 #include "../../include/qpgpu.h"
 #include "qp_common.h"
 #include "qp_kkt.h"
+#include "qp_vjp.h"
 
 extern "C" int qpk_medium_max_n(void);
 extern "C" int qpk_medium_max_m(void);
@@ -500,6 +501,58 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d, const double* G, const 
                             const double* x, const double* u, const int32_t* status, double* r,
                             void* stream) {
   return kkt_run(d, true, G, g0, CE, ce0, nullptr, nullptr, hi, lo, x, u, status, r, stream);
+}
+
+// ---- the backward step (include/qpgpu.h; kernels: qp_vjp.hip) -------------------------
+// Both entries: every rule is decided from the descriptor and the pointers' values, before any
+// array is read; no workspace, one kernel, so the first call for a shape can be captured.
+static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                   const double* CI, const double* x, const double* u, const int32_t* status,
+                   const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
+                   double* dci0, double* dhi, double* dlo, void* stream) {
+  if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
+    return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->flags != 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (box && (int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->p + d->m > 0 && !u) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0) {
+    if (!G || !x || !gx) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (d->p > 0 && !CE) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (!box && d->m > 0 && !CI) return QPGPU_ERR_INVALID_ARGUMENT;
+  }
+  // n <= 64: L, M and S of a QP fit on chip; a per-QP block is indexed with 32 bits
+  const int64_t lim = (int64_t)1 << 31;
+  if (!qpk_vjp_name(d->n) || (int64_t)d->n * d->m >= lim || (int64_t)d->n * d->p >= lim ||
+      (int64_t)d->p + d->m >= lim)
+    return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  if (d->batch == 0) return QPGPU_SUCCESS;
+  qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
+                    dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
+                    box ? dlo : nullptr};
+  const hipError_t e = qpk_launch_vjp(&a, d->layout == QPGPU_LAYOUT_TILED64, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_vjp(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* CI,
+              const double* x, const double* u, const int32_t* status, const double* gx, double* dG,
+              double* dg0, double* dCE, double* dce0, double* dCI, double* dci0, void* stream) {
+  return vjp_run(d, false, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, nullptr, nullptr, stream);
+}
+
+int qpgpu_vjp_box(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* x,
+                  const double* u, const int32_t* status, const double* gx, double* dG, double* dg0,
+                  double* dCE, double* dce0, double* dhi, double* dlo, void* stream) {
+  return vjp_run(d, true, G, CE, nullptr, x, u, status, gx, dG, dg0, dCE, dce0, nullptr, nullptr, dhi, dlo, stream);
+}
+
+const char* qpgpu_kernel_name_vjp(int32_t n, int32_t p, int32_t m) {
+  (void)p;
+  (void)m;
+  const char* k = qpk_vjp_name(n);
+  return k ? k : "";
 }
 
 // Host-pointer entry (the drop-in's path, one QP per solve_quadprog() call, and the batched

@@ -17,6 +17,7 @@ independently and identically on every rank.
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -70,6 +71,9 @@ EXPORTED_SYMBOLS = (
     "qpgpu_kernel_name_box_dual",
     "qpgpu_kkt_residuals",
     "qpgpu_kkt_residuals_box",
+    "qpgpu_vjp",
+    "qpgpu_vjp_box",
+    "qpgpu_kernel_name_vjp",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -124,6 +128,12 @@ def _load():
     lib.qpgpu_kkt_residuals.restype = ctypes.c_int
     lib.qpgpu_kkt_residuals_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
     lib.qpgpu_kkt_residuals_box.restype = ctypes.c_int
+    lib.qpgpu_vjp.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 14
+    lib.qpgpu_vjp.restype = ctypes.c_int
+    lib.qpgpu_vjp_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13
+    lib.qpgpu_vjp_box.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_vjp.argtypes = [ctypes.c_int32] * 3
+    lib.qpgpu_kernel_name_vjp.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -189,6 +199,12 @@ def kernel_name_box_dual(n: int, p: int, flags: int = 0) -> str:
     """The kernel a qpgpu_solve_batched_box_dual launch of shape (n, p) with `flags` runs ("" where
     kernel_name_box is ""); every such name contains "box" and "dual"."""
     return LIB.qpgpu_kernel_name_box_dual(n, p, flags).decode()
+
+
+def kernel_name_vjp(n: int, p: int = 0, m: int = 0) -> str:
+    """The kernel a qpgpu_vjp / qpgpu_vjp_box launch of this shape runs: a "lane" name for n <= 8, a
+    "group" name for 8 < n <= 64, "" beyond (QPGPU_ERR_UNSUPPORTED_SHAPE)."""
+    return LIB.qpgpu_kernel_name_vjp(n, p, m).decode()
 
 
 # the n > 64 default path's certification (DESIGN §3.4): a QP whose decisions the tolerance mode
@@ -458,7 +474,9 @@ class _DeviceBatchBase:
     with multipliers, KKT check)."""
 
     _INPUTS = ()
-    _ENTRY = _ENTRY_DUAL = _ENTRY_KKT = None
+    _ENTRY = _ENTRY_DUAL = _ENTRY_KKT = _ENTRY_VJP = None
+    _VJP_INPUTS = ()   # the inputs the backward step reads, in its C entry's order
+    _VJP_OUTPUTS = ()  # its six gradients, in its C entry's order
 
     def __init__(self, pr, device, with_iters: bool = True, layout=None):
         import torch
@@ -528,6 +546,56 @@ class _DeviceBatchBase:
                                              ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_KKT)
         return r
 
+    def _vjp_elems(self, name):
+        n, p, m = self.n, self.p, self.m
+        return {"dG": n * n, "dg0": n, "dCE": n * p, "dce0": p, "dCI": n * m, "dci0": m, "dhi": n, "dlo": n}[name]
+
+    def vjp(self, u, gx, outs=None, status=True, stream=None, x=None):
+        """Enqueue the backward step (qpgpu_vjp / qpgpu_vjp_box, include/qpgpu.h) of this batch's
+        resident inputs at (x, u) for gx = dl/dx on `stream` (default current): no host round
+        trip, so it can follow a dual solve on the same stream.  u as kkt_residuals() takes it; gx:
+        n float64 per QP in the layout of x; x: default this batch's own.  status=True masks by
+        this batch's status (a non-OK QP's gradients are +0.0), None or False evaluates every QP, a
+        tensor is used as given.  outs: None computes all six gradients into new tensors; otherwise
+        a dict from output name (dG, dg0, dCE, dce0 and dCI, dci0 or dhi, dlo) to the tensor to
+        write, or True to allocate it: an output that is not named is passed as NULL and not
+        computed.  Returns the dict of the tensors written, each (rows, E) in this batch's layout
+        (vjp_rows() decodes host copies)."""
+        import torch
+
+        x = self.x if x is None else x
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        rows = x.numel() // self.n
+        outs = dict.fromkeys(self._VJP_OUTPUTS, True) if outs is None else dict(outs)
+        for k in outs:
+            if k not in self._VJP_OUTPUTS:
+                raise ValueError(f"{k!r} is no output of {self._ENTRY_VJP}: {self._VJP_OUTPUTS}")
+            if outs[k] is True:
+                outs[k] = torch.empty((rows, self._vjp_elems(k)), dtype=torch.float64, device=x.device)
+        st = self.status if status is True else (None if status is None or status is False else status)
+        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        tensors = [getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st, gx] + [outs.get(k) for k in self._VJP_OUTPUTS]
+        _check(getattr(LIB, self._ENTRY_VJP)(ctypes.byref(d), *[vp(t) for t in tensors],
+                                             ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_VJP)
+        return outs
+
+    def vjp_rows(self, outs):
+        """A vjp() result as numpy arrays shaped like the inputs ((batch, n, n) for dG, ...),
+        whatever the layout."""
+        n, p, m = self.n, self.p, self.m
+        shapes = {"dG": (n, n), "dg0": (n,), "dCE": (n, p), "dce0": (p,), "dCI": (n, m), "dci0": (m,),
+                  "dhi": (n,), "dlo": (n,)}
+        res = {}
+        for k, t in outs.items():
+            h = t.cpu().numpy().reshape(-1)
+            if self.layout == LAYOUT_TILED64:
+                res[k] = from_tiled64(h, self.batch, shapes[k])
+            else:
+                res[k] = h[:self.batch * self._vjp_elems(k)].reshape((self.batch,) + shapes[k])
+        return res
+
     def kkt_rows(self, r):
         """A kkt_residuals() result as numpy (batch, 8), whatever the layout."""
         rh = r.cpu().numpy()
@@ -549,6 +617,9 @@ class DeviceBatch(_DeviceBatchBase):
     _INPUTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
     _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched", "qpgpu_solve_batched_dual"
     _ENTRY_KKT = "qpgpu_kkt_residuals"
+    _ENTRY_VJP = "qpgpu_vjp"
+    _VJP_INPUTS = ("G", "CE", "CI")
+    _VJP_OUTPUTS = ("dG", "dg0", "dCE", "dce0", "dCI", "dci0")
 
     def __init__(self, pr: Problems, device, with_iters: bool = True, layout=None):
         super().__init__(pr, device, with_iters, layout)
@@ -588,6 +659,9 @@ class DeviceBoxBatch(_DeviceBatchBase):
     _INPUTS = ("G", "g0", "CE", "ce0", "hi", "lo")
     _ENTRY, _ENTRY_DUAL = "qpgpu_solve_batched_box", "qpgpu_solve_batched_box_dual"
     _ENTRY_KKT = "qpgpu_kkt_residuals_box"
+    _ENTRY_VJP = "qpgpu_vjp_box"
+    _VJP_INPUTS = ("G", "CE")
+    _VJP_OUTPUTS = ("dG", "dg0", "dCE", "dce0", "dhi", "dlo")
 
     def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
         super().__init__(bp, device, with_iters, layout)
@@ -681,6 +755,114 @@ def kkt_residuals(pr, x, u, status=None, layout=None, device="cuda:0"):
     r = db.kkt_residuals(ud, status=sd, x=xd)
     torch.cuda.synchronize(r.device)
     return db.kkt_rows(r)
+
+
+def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None):
+    """The gradients of l with respect to the data of every QP of `pr` (Problems: qpgpu_vjp;
+    BoxProblems: qpgpu_vjp_box) at the primal-dual pair (x, u) for gx = dl/dx, computed on the GPU:
+    a dict of float64 arrays shaped like the inputs — dG (B, n, n), dg0 (B, n), dCE (B, n, p),
+    dce0 (B, p) and dCI (B, n, m), dci0 (B, m), or dhi, dlo (B, n) for bounds (include/qpgpu.h).
+    x and gx are (B, n), u is (B, p + m) in QP-major order (may be None when p + m == 0); with
+    `status` (B int32) a QP that is not QP_OK gets +0.0 everywhere.  outs: the names to compute
+    (default all six).  layout="tiled64" runs the TILED64 form (converted here on the host)."""
+    import torch
+
+    db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
+    B, E = pr.batch, pr.p + pr.m
+    conv = to_tiled64 if db.layout == LAYOUT_TILED64 else (lambda a: a)
+    up = lambda a, cols: torch.from_numpy(np.array(
+        conv(np.asarray(a, dtype=np.float64).reshape(B, cols)), dtype=np.float64, order="C")).to(device)
+    xd, gd = up(x, pr.n), up(gx, pr.n)
+    ud = up(u, E) if E > 0 else None
+    sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
+    res = db.vjp(ud, gd, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd)
+    torch.cuda.synchronize(xd.device)
+    return db.vjp_rows(res)
+
+
+@functools.lru_cache(maxsize=None)
+def _layer_functions():
+    """The two torch.autograd.Functions behind qp_layer / qp_layer_box (built at first use: torch is
+    imported lazily everywhere in this module)."""
+    import torch
+
+    def run(box, ctx, G, g0, CE, ce0, c5, c6):
+        B, n, p = G.shape[0], G.shape[-1], CE.shape[-1]
+        m = 2 * n if box else c5.shape[-1]
+        for t in (G, g0, CE, ce0, c5, c6):
+            if t.dtype != torch.float64 or not t.is_cuda:
+                raise ValueError("qp_layer takes float64 tensors on the GPU")
+        ins = [t.detach().contiguous() for t in (G, g0, CE, ce0, c5, c6)]
+        dev = G.device
+        x = torch.zeros((B, n), dtype=torch.float64, device=dev)
+        f = torch.empty(B, dtype=torch.float64, device=dev)
+        st = torch.empty(B, dtype=torch.int32, device=dev)
+        u = torch.zeros((B, p + m), dtype=torch.float64, device=dev)
+        d = ProblemDesc(n, p, m, 0, B, 0, LAYOUT_QP_MAJOR)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        entry = "qpgpu_solve_batched_box_dual" if box else "qpgpu_solve_batched_dual"
+        _check(getattr(LIB, entry)(ctypes.byref(d), *[vp(t) for t in ins], vp(x), vp(f), vp(st), None, vp(u),
+                                   None, stream), entry)
+        ctx.save_for_backward(ins[0], ins[2], ins[4], x, u, st)
+        ctx.shape = (B, n, p, m)
+        return x
+
+    def back(box, ctx, gx):
+        G, CE, c5, x, u, st = ctx.saved_tensors
+        B, n, p, m = ctx.shape
+        need = ctx.needs_input_grad
+        sizes = ((B, n, n), (B, n), (B, n, p), (B, p)) + (((B, n), (B, n)) if box else ((B, n, m), (B, m)))
+        outs = [torch.empty(sz, dtype=torch.float64, device=G.device) if nd else None for sz, nd in zip(sizes, need)]
+        d = ProblemDesc(n, p, m, 0, B, 0, LAYOUT_QP_MAJOR)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(G.device).cuda_stream)
+        gx = gx.contiguous()
+        if box:
+            rc = LIB.qpgpu_vjp_box(ctypes.byref(d), vp(G), vp(CE), vp(x), vp(u), vp(st), vp(gx),
+                                   *[vp(t) for t in outs], stream)
+        else:
+            rc = LIB.qpgpu_vjp(ctypes.byref(d), vp(G), vp(CE), vp(c5), vp(x), vp(u), vp(st), vp(gx),
+                               *[vp(t) for t in outs], stream)
+        _check(rc, "qpgpu_vjp_box" if box else "qpgpu_vjp")
+        return tuple(outs)
+
+    class QpLayer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, G, g0, CE, ce0, CI, ci0):
+            return run(False, ctx, G, g0, CE, ce0, CI, ci0)
+
+        @staticmethod
+        def backward(ctx, gx):
+            return back(False, ctx, gx)
+
+    class QpLayerBox(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, G, g0, CE, ce0, hi, lo):
+            return run(True, ctx, G, g0, CE, ce0, hi, lo)
+
+        @staticmethod
+        def backward(ctx, gx):
+            return back(True, ctx, gx)
+
+    return QpLayer, QpLayerBox
+
+
+def qp_layer(G, g0, CE, ce0, CI, ci0):
+    """The batched QP as a differentiable layer: x* (B, n) of
+        min 0.5 x^T G x + g0^T x   s.t.  CE^T x + ce0 = 0,  CI^T x + ci0 >= 0
+    for float64 device tensors G (B, n, n), g0 (B, n), CE (B, n, p), ce0 (B, p), CI (B, n, m),
+    ci0 (B, m), QP-major.  Forward is qpgpu_solve_batched_dual, backward qpgpu_vjp on the current
+    stream with no host round trip; an input that does not require grad gets none (its gradient
+    is not computed), and no gradient flows through a QP whose status is not QP_OK (+0.0; its x is
+    whatever the solve left: zeros for a G that is not positive definite)."""
+    return _layer_functions()[0].apply(G, g0, CE, ce0, CI, ci0)
+
+
+def qp_layer_box(G, g0, CE, ce0, hi, lo):
+    """qp_layer for bounds lo <= x <= hi (hi, lo: (B, n)): qpgpu_solve_batched_box_dual forward,
+    qpgpu_vjp_box backward."""
+    return _layer_functions()[1].apply(G, g0, CE, ce0, hi, lo)
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):

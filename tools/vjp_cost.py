@@ -1,0 +1,153 @@
+"""Kernel time of qpgpu_vjp beside the dual solve that produces its inputs.
+
+For each shape (default: C1 = 65 536 x (7, 6, 14) and C3 = 16 384 x (30, 6, 60)) and each layout,
+two things are launched in turn on one stream, each between its own HIP-event pair:
+  (a) qpgpu_vjp with all six gradients requested and status given, on the (x, u, status) that
+      qpgpu_solve_batched_dual left on the device, gx standard normal;
+  (b) qpgpu_solve_batched_dual of the same QPs.  With --parent-lib PATH the solve is launched from
+      that build of libqpgpu.so (the parent commit's) on the same device arrays; without it, from
+      the library under test, whose solver kernels are the parent's.
+Inputs rotate over R resident sets (set r = set 0 rolled by r*B/R QPs, whole tiles) that together
+exceed twice the Infinity Cache, so every launch reads cold inputs; untimed launches of both run
+first.  Prints one JSON line per shape and layout: median / min / max ms, the ratio of the
+medians, and the bytes moved by the backward step (read: G, CE, x, u, gx, status and the working
+columns of CI; written: the six gradients, dCI's zero columns included).
+
+    python tools/vjp_cost.py [--reps 20] [--parent-lib PATH] [--out profiles/vjp_cost/vjp_cost.log]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "motion-generation-using-quadratic-programs_amd"))
+
+MALL_BYTES = 256 << 20
+SHAPES = {"C1": (7, 6, 14, 65536), "C2": (8, 0, 16, 65536), "mgqp": (14, 10, 28, 65536),
+          "C3": (30, 6, 60, 16384), "n64": (64, 0, 128, 2048)}
+INPUTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
+
+
+def main():
+    import torch
+
+    import qpgpu
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20, help="timed launches of each kind per shape and layout")
+    ap.add_argument("--warm-ms", type=float, default=200.0)
+    ap.add_argument("--shapes", default="C1,C3")
+    ap.add_argument("--layouts", default="qp_major,tiled64")
+    ap.add_argument("--parent-lib", default=None, help="a libqpgpu.so of the parent commit for the dual solve")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream(dev)
+    solve_lib = qpgpu.LIB
+    if args.parent_lib:  # its own copies of the library's internal symbols, not the loaded library's
+        solve_lib = ctypes.CDLL(os.path.abspath(args.parent_lib), mode=os.RTLD_LOCAL | os.RTLD_NOW | os.RTLD_DEEPBIND)
+        solve_lib.qpgpu_solve_batched_dual.argtypes = [ctypes.POINTER(qpgpu.ProblemDesc)] + [ctypes.c_void_p] * 13
+        solve_lib.qpgpu_solve_batched_dual.restype = ctypes.c_int
+    lines = []
+    for name in args.shapes.split(","):
+        n, p, m, B = SHAPES[name]
+        E = {"G": n * n, "g0": n, "CE": n * p, "ce0": p, "CI": n * m, "ci0": m}
+        pr = qpgpu.make_problems("general", n, p, m, 0, B, seed=2026)
+        in_bytes = 8 * sum(E.values()) * B
+        R = max(2, -(-2 * MALL_BYTES // in_bytes) + 1)
+        for layout in args.layouts.split(","):
+            base = qpgpu.DeviceBatch(pr, dev, with_iters=False, layout=layout)
+            sets = []
+            for r in range(R):
+                if r == 0:
+                    db = base
+                else:
+                    db = qpgpu.DeviceBatch(pr.slice(0, 1), dev, with_iters=False, layout=layout)  # a shell
+                    db.batch = B
+                    q0 = r * (B // R) // 64 * 64
+                    for k in INPUTS:
+                        t = getattr(base, k)
+                        setattr(db, k, torch.roll(t.reshape(-1), shifts=q0 * E[k], dims=0).reshape(t.shape).contiguous())
+                    for k in ("x", "f", "status"):
+                        setattr(db, k, torch.zeros_like(getattr(base, k)))
+                rows = db.x.shape[0]
+                db.u = torch.zeros((rows, p + m), dtype=torch.float64, device=dev)
+                db.gx = torch.randn((rows, n), dtype=torch.float64, device=dev)
+                db.grads = {k: torch.empty((rows, db._vjp_elems(k)), dtype=torch.float64, device=dev)
+                            for k in db._VJP_OUTPUTS}
+                d = qpgpu.ProblemDesc(n, p, m, 0, B, 0, db.layout)
+                vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+                db.solve_args = (d, [ctypes.byref(d)] + [vp(getattr(db, k)) for k in INPUTS]
+                                 + [vp(db.x), vp(db.f), vp(db.status), None, vp(db.u), None,
+                                    ctypes.c_void_p(s.cuda_stream)])
+                sets.append(db)
+
+            def solve(q):
+                rc = solve_lib.qpgpu_solve_batched_dual(*sets[q % R].solve_args[1])
+                assert rc == 0, rc
+
+            def vjp(q):
+                db = sets[q % R]
+                db.vjp(db.u, db.gx, outs=db.grads, stream=s)
+
+            def timed(fn, q):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                fn(q)
+                e1.record(s)
+                e1.synchronize()
+                return e0.elapsed_time(e1)
+
+            for q in range(R):  # every set's (x, u, status)
+                solve(q)
+            torch.cuda.synchronize()
+            t0, q = time.perf_counter(), 0
+            while q < 4 or (time.perf_counter() - t0) * 1e3 < args.warm_ms:
+                vjp(q)
+                solve(q)
+                q += 1
+                torch.cuda.synchronize()
+            ms = {"vjp": [], "solve": []}
+            for k in range(args.reps):
+                q += 1
+                ms["vjp"].append(timed(vjp, q))
+                ms["solve"].append(timed(solve, q))
+            st = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+            db = sets[0]
+            uh = db.u.cpu().numpy().reshape(-1)
+            uh = qpgpu.from_tiled64(uh, B, (p + m,)) if layout == "tiled64" else uh.reshape(-1, p + m)[:B]
+            ok = (db.status == 0).cpu().numpy()
+            nact = (uh[:, p:] != 0).sum(axis=1)
+            read = 8 * B * (n * n + n * p + n + (p + m) + n) + 4 * B + 8 * n * int(nact[ok].sum())
+            written = 8 * B * (n * n + n + n * p + p + n * m + m)
+            g = db.vjp_rows(db.grads)
+            tv = np.median(ms["vjp"]) * 1e-3
+            rec = {"shape": name, "n": n, "p": p, "m": m, "batch": B, "layout": layout, "input_sets": R,
+                   "reps": args.reps, "vjp_kernel": qpgpu.kernel_name_vjp(n, p, m),
+                   "solve_kernel": qpgpu.kernel_name(n, p, m), "solve_lib": args.parent_lib or "under test",
+                   "vjp_ms": st(ms["vjp"]), "dual_solve_ms": st(ms["solve"]),
+                   "vjp_over_dual_solve": float(np.median(ms["vjp"]) / np.median(ms["solve"])),
+                   "vjp_bytes_read": read, "vjp_bytes_written": written,
+                   "vjp_GBps": (read + written) / tv * 1e-9,
+                   "ok_qps": int(ok.sum()), "mean_active_inequalities": float(nact[ok].mean()) if ok.any() else None,
+                   "all_finite": bool(all(np.all(np.isfinite(v)) for v in g.values())),
+                   "vjp_raw_ms": [round(v, 4) for v in ms["vjp"]],
+                   "dual_solve_raw_ms": [round(v, 4) for v in ms["solve"]]}
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+            del sets, base
+            torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
