@@ -357,6 +357,35 @@ constexpr int kStampSlots = 18;
 enum Mode { kPlain = 0, kDual = 1, kBox = 2, kBoxDual = 3 };
 inline Mode mode_of(const QpArgs& a) { return Mode((a.u ? kDual : kPlain) | (a.hi ? kBox : kPlain)); }
 
+// QPs [b0, b0 + count) of a's batch (host side): every per-QP pointer advanced to QP b0's block in
+// a's layout (TILED64: b0 a multiple of 64, so a whole-tile boundary), NULL left NULL.  stamps,
+// which is per wave, stays the caller's.
+inline QpArgs sub_range(const QpArgs& a, int64_t b0, int64_t count) {
+  const int64_t n = a.n, p = a.p, m = a.m;
+  const auto blocks = [&](auto* q, int64_t E) { return q ? q + (a.tile == 64 ? b0 / 64 * 64 * E : b0 * E) : q; };
+  const auto each = [&](auto* q) { return q ? q + b0 : q; };
+  QpArgs c = a;
+  c.batch = count;
+  c.G = blocks(a.G, n * n);
+  c.g0 = blocks(a.g0, n);
+  c.CE = blocks(a.CE, n * p);
+  c.ce0 = blocks(a.ce0, p);
+  c.CI = blocks(a.CI, n * m);
+  c.ci0 = blocks(a.ci0, m);
+  c.x = blocks(a.x, n);
+  c.f = each(a.f);
+  c.status = each(a.status);
+  c.iters = each(a.iters);
+  c.x_eq = blocks(a.x_eq, n);
+  c.f_eq = each(a.f_eq);
+  c.st_eq = each(a.st_eq);
+  c.u = blocks(a.u, p + m);
+  c.nact = each(a.nact);
+  c.hi = blocks(a.hi, n);
+  c.lo = blocks(a.lo, n);
+  return c;
+}
+
 // internal QpArgs.flags bit set by the host when CI and ci0 are 16-byte aligned
 constexpr uint32_t kArgAligned16 = 0x80000000u;
 // internal QpArgs.flags bit set by the host when G, g0 and (with p > 0) CE and ce0 are 16-byte

@@ -71,6 +71,11 @@
 #ifndef QPGPU_LANE_STAMPS
 #define QPGPU_LANE_STAMPS 1
 #endif
+#if defined(QPGPU_LANE_OCC2) || defined(QPGPU_LANE_DMA_P0) || defined(QPGPU_LANE_CE_LATE) ||       \
+    defined(QPGPU_LANE_WARMUP) || defined(QPGPU_LANE_LOOPTOP_EXIT) || defined(QPGPU_LANE_FULL) || \
+    defined(QPGPU_LANE_AB_C1ONLY) || defined(QPGPU_LANE_AB_N8P0ONLY)
+#error "retired build switch: its default is folded into qp_lane.hip; the other side is an earlier revision (DESIGN 5.15, tools/ab_build.sh SRCFILE=)"
+#endif
 
 namespace QPK_LANE_NS {
 using namespace qpk;
@@ -106,54 +111,33 @@ __device__ __forceinline__ double from_agpr(const AgprD& a) {
 }
 
 constexpr int kQpw = 64;      // QPs per wave: one per lane
-// Two waves per SIMD (QPGPU_LANE_OCC2, an A/B build for VERDICT r05 item 6): 256 registers per
-// lane and a 20 KiB stage (eight waves per CU); G and CE no longer stage, each lane loads its own
-// from global memory, and the LDS copy of CI shrinks to the rows the smaller stage holds.
-#ifndef QPGPU_LANE_OCC2
-#define QPGPU_LANE_OCC2 0
-#endif
-constexpr int kLaneOcc = QPGPU_LANE_OCC2 ? 2 : 1;
-constexpr int kStage = QPGPU_LANE_OCC2 ? 2560 : 5120;  // staging buffer, doubles (40 KiB: 4 waves per CU)
+// One wave per SIMD: 512 registers per lane and a 40 KiB stage, four waves per CU.  Two waves per
+// SIMD (256 registers, a 20 KiB stage, G and CE loaded per lane from global memory) measured
+// 85.5 us against 40.4 on C1 and was not kept.
+constexpr int kLaneOcc = 1;
+constexpr int kStage = 5120;  // staging buffer, doubles (40 KiB: 4 waves per CU)
 // The first l1 scan (which fills the on-chip CI copy) is software-pipelined two rows deep: row
 // j+1's loads are issued (and fenced from the scheduler) before row j is consumed, so one memory
 // latency covers two rows instead of the scheduler's one-load-at-a-time minimum-pressure order.
 constexpr int kScanDepth = 2;
-// p = 0 (no equality phase): copy CI rows into LDS by DMA at the end of the setup (1) or let the
-// first scan load them (0).  Measured on C2 (profiles/r03_s6): 83.6 us with the DMA, 72.9 without
-// — the DMA's per-lane 16-B pieces take ~23k cycles per wave to issue, the first scan's direct
-// loads 18.5k, and nothing hides either — so 0; with p > 0 the equality phase hides the DMA.
-// 2: a part per Cholesky row (profiles/r06_s15: 75.2 us per launch against 67.6-68.0 with 0,
-// pipelined 1.489e9 against 1.449e9 solves/s — an A/B value, not the default).
-#ifndef QPGPU_LANE_DMA_P0
-#define QPGPU_LANE_DMA_P0 0
-#endif
-// Where the DMA path touches the CI rows past the LDS copy and ci0 (one dword per 128-B line)
-// ahead of the first scan: 0 = nowhere, the first scan loads them (the product since round 5),
-// 1 = after the CE -> AGPR move (rounds 3-4), 2 = at the last equality step.  Measured on C1
-// (profiles/r05_s3): FETCH 146.4 / 125.0 / 130.1 MB for 1 / 0 / 2 — the touched lines leave L2
-// before the first scan reads them, so the touch only adds a second fetch — at 44.6 / 44.8 /
-// 45.7 us (two runs each; 0 and 1 within the run-to-run spread).
-// Where the setup waits for round B (CE / ce0 into LDS): 1 = after J = L^-T and the solve, which
-// need only the factor, 0 = right after the Cholesky (rounds 1-4; A/B only)
-#ifndef QPGPU_LANE_CE_LATE
-#define QPGPU_LANE_CE_LATE 1
-#endif
-#ifndef QPGPU_LANE_WARMUP
-#define QPGPU_LANE_WARMUP 0
-#endif
-// The fast build's invalid-fast-form check at the top of every loop pass as well (1, the
-// product since round 5) or only after the equality phase and after the loop (0); 2 = compiled
-// in but never taken (A/B only).  Round 4 dropped it after a wrong-result run that no committed
-// source reproduces (profiles/r05_s2, r05_s3).
-#ifndef QPGPU_LANE_LOOPTOP_EXIT
-#define QPGPU_LANE_LOOPTOP_EXIT 1
-#endif
-// The full-wave aligned kernels (lane_body's FULL; qp_lane_full_kernel) for the whole 64-QP
-// blocks of a C1 / C4 / C2-shaped launch: 1 = the product, 0 = every launch runs the general
-// body (A/B only).
-#ifndef QPGPU_LANE_FULL
-#define QPGPU_LANE_FULL 1
-#endif
+// Choices of the staging that measurements settled (the other sides: DESIGN §5.15):
+//   * p = 0 (no equality phase): the first scan loads the CI rows, no DMA copies them into LDS.
+//     Measured on C2 (profiles/r03_s6): 83.6 us with the DMA at the end of the setup, 72.9
+//     without — the DMA's per-lane 16-B pieces take ~23k cycles per wave to issue, the first
+//     scan's direct loads 18.5k, and nothing hides either; a part per Cholesky row measured 75.2 us
+//     per launch against 67.6-68.0 (profiles/r06_s15).  With p > 0 the equality phase hides the DMA.
+//   * The DMA path does not touch the CI rows past the LDS copy and ci0 ahead of the first scan,
+//     which loads them (the product since round 5).  Measured on C1 (profiles/r05_s3): FETCH
+//     146.4 / 125.0 / 130.1 MB for a touch after the CE -> AGPR move (rounds 3-4) / none / one at
+//     the last equality step — the touched lines leave L2 before the first scan reads them, so the
+//     touch only adds a second fetch — at 44.6 / 44.8 / 45.7 us (two runs each; the first two
+//     within the run-to-run spread).
+//   * The setup waits for round B (CE / ce0 into LDS) after J = L^-T and the solve, which need
+//     only the factor, not right after the Cholesky (rounds 1-4).
+//   * The fast build checks for an invalid fast form at the top of every loop pass as well (the
+//     product since round 5), not only after the equality phase and after the loop.  Round 4
+//     dropped the check after a wrong-result run that no committed source reproduces (DESIGN §5.6,
+//     profiles/r05_s2, r05_s3).
 
 // ---- arithmetic of the fast build (frcp, rcp_ok, ldiv_r, ldiv, ldistance): qp_common.h,
 // shared with the lane-pair kernel (qp_pair.hip).
@@ -288,9 +272,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // then rows 0..kCiRows-1 of every lane's CI for the active-set loop (16-B pieces, piece k of
   // lane l at doubles (k*64 + l)*2).  RB, at the top, stages g0.
   constexpr int RB = (STAGE - kQpw * NM) / 2 * 2;
-  // G and g0 stage through LDS when they fit (the product); else each lane loads its own
-  constexpr bool kStageG = RB >= kQpw * NM * NM;
-  static_assert(kStageG || QPGPU_LANE_OCC2, "G and g0 staging exceed the stage buffer");
+  // G and g0 stage through LDS
+  static_assert(RB >= kQpw * NM * NM, "G and g0 staging exceed the stage buffer");
   // CI rows held in LDS through the loop (EXACT QP-major shapes)
   constexpr int kCiRowsFit = (RB / kQpw) / MM;
   constexpr int kCiRows = (!BOX && EXACT && T == 1 && MM % 2 == 0) ? (kCiRowsFit < NM ? kCiRowsFit : NM) : 0;
@@ -300,7 +283,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // Cache after a cache warm-up (that re-read was 11k of a wave's ~88k cycles, profiles/r03_s3).
   // With p > 0 the CE / ce0 staging occupies the LDS then, so once it has landed it moves to
   // AGPRs (ceag, read back once per equality step) and the DMA takes its place.
-  constexpr bool kCiDma = kCiRows > 0 && (PX > 0 || (PX == 0 && QPGPU_LANE_DMA_P0));
+  // With p = 0 there is no equality phase to hide the copy behind: the first scan loads the rows.
+  constexpr bool kCiDma = kCiRows > 0 && PX > 0;
   constexpr int kCeN = PX > 0 ? NM * PX + PX : 1;  // CE (n x p) then ce0 (p)
   [[maybe_unused]] AgprD ceag[kCiDma ? kCeN : 1];
   const bool dma = kCiDma && (FULL || (a.flags & kArgAligned16));
@@ -366,10 +350,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     double Gr[NM][NM];
     // round A: G and g0
     const int offg0 = RB;
-    if constexpr (kStageG) {
-      stage_all(a.G, n * n, 0);
-      stage_all(a.g0, n, offg0);
-    }
+    stage_all(a.G, n * n, 0);
+    stage_all(a.g0, n, offg0);
     __syncthreads();
     // The LDS reads are unconditional (in range for every lane; an idle lane's slot holds stale
     // data that the select drops): a read under `live` becomes one exec-masked block per element,
@@ -379,18 +361,10 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     for (int i = 0; i < NM; i++) {
 #pragma unroll
       for (int j = 0; j < NM; j++) {
-        double v;
-        if constexpr (kStageG)
-          v = (i < n && j < n) ? rd_all(0, n * n, i * n + j) : 0.0;
-        else
-          v = (live && i < n && j < n) ? view(const_cast<double*>(a.G), n * n)[(i * n + j) * T] : 0.0;
+        const double v = (i < n && j < n) ? rd_all(0, n * n, i * n + j) : 0.0;
         Gr[i][j] = live ? v : 0.0;
       }
-      double v0;
-      if constexpr (kStageG)
-        v0 = i < n ? rd_all(offg0, n, i) : 0.0;
-      else
-        v0 = (live && i < n) ? view(const_cast<double*>(a.g0), n)[i * T] : 0.0;
+      const double v0 = i < n ? rd_all(offg0, n, i) : 0.0;
       g0v[i] = live ? v0 : 0.0;
     }
     __syncthreads();
@@ -429,10 +403,6 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
 #pragma unroll
     for (int i = 0; i < NM; i++) {
       round_b(i, NM);  // every lane (the copy is per wave)
-      // p = 0 (no round B, no equality phase): the CI copy a part per Cholesky row instead
-      // (QPGPU_LANE_DMA_P0 = 2; G has left the LDS for registers at the barrier above)
-      if constexpr (kCiDma && PX == 0 && QPGPU_LANE_DMA_P0 == 2)
-        if (dma) dma_ci_part(i, NM);
       if (i < n && chol_ok) {
         double sum = Gr[i][i];
 #pragma unroll
@@ -465,7 +435,10 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         for (int j = 0; j < NM; j++)
           if (i < n && j < n) Gw[(i * n + j) * T] = Gr[i][j];
     }
-    // round B lands: the staged CE / ce0 are read in the equality phase
+    // round B lands: the staged CE / ce0 are read in the equality phase.  Called once, after
+    // J = L^-T and the solve (which need only the factor), so the CE transfer lands under them
+    // instead of stalling the wave after the Cholesky.  (A lambda still: with the body written
+    // out at the call the kernels' instruction order changes, profiles/ab_retire/README.md.)
     auto land_round_b = [&]() {
     if (p > 0) {
       const int np_ = n * p;
@@ -473,7 +446,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       ce_staged = offc + kQpw * p <= STAGE;
       __syncthreads();
       lstamp(a, 10);  // diagnostic: round B (CE) landed
-      if constexpr (kCiDma && PX > 0) {
+      if constexpr (kCiDma) {
         if (dma && ce_staged) {
           // CE / ce0 -> AGPRs, then the LDS is the CI copy's (round C)
 #pragma unroll
@@ -489,17 +462,14 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
           ce_agpr = true;
           __syncthreads();
           lstamp(a, 11);  // diagnostic: CE in AGPRs
-          // the rows past the LDS copy (and ci0) warmed here; the copy itself goes a part per
-          // equality step.  Measured (profiles/r03_s10): C1 kernel 47.4 us with the warm-up
-          // here, 48.6 without it, 49.9 with it at the first equality step
-          if constexpr (QPGPU_LANE_WARMUP == 1) warmup();
+          // (the copy itself goes a part per equality step; the rows past it and ci0 are not
+          // warmed here.  Round 3 measured the C1 kernel at 47.4 us with a warm-up here, 48.6
+          // without it, 49.9 with it at the first equality step, profiles/r03_s10; round 5's
+          // fetch counts, at kScanDepth above, settled it the other way)
         }
       }
     }
     };
-    // QPGPU_LANE_CE_LATE: wait for round B after J = L^-T and the solve (which need only the
-    // factor), so the CE transfer lands under them instead of stalling the wave after the Cholesky
-    if constexpr (!QPGPU_LANE_CE_LATE) land_round_b();
     if (chol_ok) {
       // J = L^{-T}: row r of J = L^{-1} e_r (forward_elimination); c2 = trace(J).
       // With a finite L the first r entries of L^{-1} e_r are exactly +0.0 (0.0 - L*(+0) and
@@ -572,15 +542,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         if (i < n) fval += g0v[i] * xv[i];
       fval = 0.5 * fval;
     }
-    if constexpr (QPGPU_LANE_CE_LATE) land_round_b();
-  }
-  if constexpr (kCiDma && PX == 0) {
-    // no equality phase to hide the copy behind: issued after the setup, all at once (the first
-    // scan waits for it either way; during the Cholesky its issue stalls the setup's compute)
-    if (dma) {
-      if constexpr (QPGPU_LANE_DMA_P0 != 2) dma_ci_part(0, 1);
-      warmup();
-    }
+    land_round_b();
   }
   lstamp(a, 1);
   // Without the DMA: touch every cache line of this lane's CI and ci0 blocks before the
@@ -859,11 +821,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   bool done = !ok_lane;
 #pragma unroll
   for (int i = 0; i <= NM; i++) {
-    if constexpr (kCiDma && PX > 0) {
+    if constexpr (kCiDma) {
       if (ce_agpr && i < PX) dma_ci_part(i, PX);  // every lane (the copy is per wave)
-      if constexpr (QPGPU_LANE_WARMUP == 2) {
-        if (ce_agpr && i == PX - 1) warmup();
-      }
     }
     if (i < p && !done) {
       iq = i;
@@ -873,7 +832,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         const int offc = (kQpw * np_ + 127) / 128 * 128;
 #pragma unroll
         for (int j = 0; j < NM; j++) {
-          if constexpr (kCiDma && PX > 0) {
+          if constexpr (kCiDma) {
             if (ce_agpr) {
               // (idle lanes' ceag already holds zeros)
               npv[j] = j < n ? from_agpr(ceag[(j * PX + i) < kCeN ? j * PX + i : 0]) : 0.0;
@@ -888,7 +847,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
           }
         }
         bool c0_done = false;
-        if constexpr (kCiDma && PX > 0) {
+        if constexpr (kCiDma) {
           if (ce_agpr) {
             c0 = from_agpr(ceag[NM * PX + i < kCeN ? NM * PX + i : 0]);
             c0_done = true;
@@ -948,7 +907,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     a.f_eq[b] = fval;
     a.st_eq[b] = status;
   }
-  if constexpr (T == 1 && (kLanePrefetch || kCiDma)) {
+  if constexpr (T == 1 && kLanePrefetch) {
     if (live && warmed)  // the warm-up loads retire here, long after they landed
 #pragma unroll
       for (int k = 0; k < kPfCI + kPfC0; k++) asm volatile("" ::"v"(pf[k]));
@@ -960,7 +919,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   const bool ci_lds = kCiRows > 0 && (FULL || (a.flags & kArgAligned16));
   bool ci_ready = false;  // wave-uniform: the on-chip copy has been written (or has landed)
   if constexpr (kCiDma) {
-    if (dma && (PX == 0 || ce_agpr)) {
+    if (dma && ce_agpr) {
       __syncthreads();  // the DMA has landed
       ci_ready = true;
     }
@@ -971,8 +930,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // Fast build: a fast form that went out of range in the setup or the equality phase (or
   // non-finite data) sends the wave to the IEEE re-solve now, instead of after a loop that
   // would run on garbage up to the step cap.  (The CE / CI copies into LDS have landed: the
-  // re-solve may restage.)  The loop checks again at the top of every pass
-  // (QPGPU_LANE_LOOPTOP_EXIT) and after the last one.
+  // re-solve may restage.)  The loop checks again at the top of every pass and after the last one.
   if constexpr (F) {
     if (wave_any(!fok)) return false;
   }
@@ -1194,11 +1152,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     uint64_t tscan = 0, tsel = 0, nloop = 0, tfirst = 0;  // diagnostic stamps only
     [[maybe_unused]] uint64_t tdzr = 0, tstep = 0;        // (QPGPU_LANE_STAMPS == 2: l2a split)
     while (wave_any(active)) {
-      if constexpr (F && QPGPU_LANE_LOOPTOP_EXIT == 1) {
+      if constexpr (F) {
         if (wave_any(!fok)) return false;
-      }
-      if constexpr (F && QPGPU_LANE_LOOPTOP_EXIT == 2) {
-        if (wave_any(!fok) && a.max_steps < -1) return false;
       }
       const uint64_t tl0 = (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
       scan_pass();
@@ -1446,7 +1401,7 @@ __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
 // C1 / C4 (7, 6, 14) and C2 (7, 0, 14), in both layouts.  Kernels of their own, not a branch in the
 // kernels above (which stay the code they were; a branch in the kernel once pushed the N = 8
 // instantiations into scratch, profiles/placement/kernel_regs_branch_in_kernel.txt).
-#if QPGPU_LANE_FULL && !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED && !QPGPU_LANE_OCC2
+#if !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED
 #define QPK_LANE_HAS_FULL 1
 template <int NM, int MM, int T, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_full_kernel(const QpArgs a) {
@@ -1469,9 +1424,9 @@ static bool full_wave_launch(const QpArgs&) {
 }
 #endif
 // The whole 64-QP blocks of the batch through `full`, the remaining QPs (batch % 64) through
-// `rest` as a second launch on the same stream with every per-QP pointer advanced past those
-// blocks.  A whole number of 64-QP blocks is a whole number of tiles and of 512-byte steps, so
-// the remainder's arrays keep the layout and the 16-byte residues the host checked.
+// `rest` as a second launch on the same stream over the sub-range past those blocks.  A whole
+// number of 64-QP blocks is a whole number of tiles and of 512-byte steps, so the remainder's
+// arrays keep the layout and the 16-byte residues the host checked.
 template <class Full, class Rest>
 static void launch_full_then_rest(const QpArgs& a, Full&& full, Rest&& rest) {
   const int64_t nb = a.batch / kQpw, done = nb * kQpw;
@@ -1482,21 +1437,8 @@ static void launch_full_then_rest(const QpArgs& a, Full&& full, Rest&& rest) {
     qpk_lane_count_launch(1);
   }
   if (a.batch > done) {
-    const int64_t n = a.n, p = a.p, m = a.m;
-    const auto blocks = [&](auto* q, int64_t E) { return q ? q + done * E : q; };
-    const auto each = [&](auto* q) { return q ? q + done : q; };
-    QpArgs c = a;
-    c.batch = a.batch - done;
-    c.G = blocks(a.G, n * n);
-    c.g0 = blocks(a.g0, n);
-    c.CE = blocks(a.CE, n * p);
-    c.ce0 = blocks(a.ce0, p);
-    c.CI = blocks(a.CI, n * m);
-    c.ci0 = blocks(a.ci0, m);
-    c.x = blocks(a.x, n);
-    c.f = each(a.f);
-    c.status = each(a.status);
-    c.stamps = a.stamps ? a.stamps + nb * kStampSlots : nullptr;
+    QpArgs c = sub_range(a, done, a.batch - done);
+    c.stamps = a.stamps ? a.stamps + nb * kStampSlots : nullptr;  // (per wave, not per QP)
     rest(c, dim3(1));
     qpk_lane_count_launch(0);
   }
@@ -1568,27 +1510,6 @@ static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
     case kPlain:
       break;
   }
-// A/B builds with one instantiation only refuse every other launch with an error: a launch
-// they skipped silently once returned the previous call's f / status / passes through the host
-// entry's reused device buffers, with x = 0 (profiles/r05_s26)
-#ifdef QPGPU_LANE_AB_C1ONLY
-  // A/B experiment builds (tools/ab_build.sh): only the C1 instantiation, for a quick compile
-  if constexpr (NM == 7 && MM == 14 && T == 1)
-    if (a.n == NM && a.m == MM && !a.x_eq && a.p == 6) {
-      hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 6>), g, blk, 0, stream, a);
-      return hipSuccess;
-    }
-  return hipErrorInvalidValue;
-#endif
-#ifdef QPGPU_LANE_AB_N8P0ONLY
-  // A/B / ISA-study builds: only the QP-major (8, 0, 16) instantiation
-  if constexpr (NM == 8 && MM == 16 && T == 1)
-    if (a.n == NM && a.m == MM && !a.x_eq && a.p == 0) {
-      hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 0>), g, blk, 0, stream, a);
-      return hipSuccess;
-    }
-  return hipErrorInvalidValue;
-#endif
   if (a.n == NM && a.m == MM && !a.x_eq) {
 #if QPK_LANE_HAS_FULL
     if constexpr (NM == 7 && MM == 14)

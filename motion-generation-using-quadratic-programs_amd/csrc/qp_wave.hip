@@ -43,6 +43,16 @@
 #define QPK_WAVE_NS qpk
 #define QP_WAVE_KERNEL qp_wave_kernel
 #endif
+#if defined(QPGPU_WAVE_S16) || defined(QPGPU_WAVE_FALLTHRU) || defined(QPGPU_WAVE_RPACK) ||         \
+    defined(QPGPU_WAVE_REGSETUP) || defined(QPGPU_WAVE_URPF) || defined(QPGPU_WAVE_PRESEL) ||       \
+    defined(QPGPU_WAVE_HCHAIN2) || defined(QPGPU_WAVE_SWEEP2) || defined(QPGPU_WAVE_TOLLOOP) ||     \
+    defined(QPGPU_WAVE_GJR_CAP) || defined(QPGPU_WAVE_SHADOW) || defined(QPGPU_WAVE_KUL) ||         \
+    defined(QPGPU_WAVE_KUJ) || defined(QPGPU_WAVE_KUDZ) || defined(QPGPU_WAVE_URU) ||               \
+    defined(QPGPU_WAVE_HCU) || defined(QPGPU_WAVE_SCANKG) || defined(QPGPU_WAVE_SCANKG4) ||         \
+    defined(QPGPU_WAVE_SHADOW_U) || defined(QPGPU_WAVE_SHADOW_KP) || defined(QPGPU_WAVE_TOLCH) ||   \
+    defined(QPGPU_WAVE_OCC4_LDS) || defined(QPGPU_WAVE_OCC_SMALL) || defined(QPGPU_WAVE_GJR_OCC)
+#error "retired build switch: its default is folded into qp_wave.hip (the tunables are plain constants there); the other side is an earlier revision (DESIGN 5.15, tools/ab_build.sh SRCFILE=)"
+#endif
 
 namespace QPK_WAVE_NS {
 using namespace qpk;
@@ -114,18 +124,9 @@ __device__ __forceinline__ void grp_sync() {
 // stay strictly sequential in the reference's index order, so results are bit-identical.
 // Chunk sizes: operands in global memory (CI always; J and R with GJR) batch kUG loads per
 // chunk; LDS-resident operands batch kUL.
-#ifndef QPGPU_WAVE_KUL
-#define QPGPU_WAVE_KUL 4
-#endif
-// J columns of a Givens sweep loaded per chunk (LDS-resident J)
-#ifndef QPGPU_WAVE_KUJ
-#define QPGPU_WAVE_KUJ 4
-#endif
-// chunk of compute_d_z's LDS sums (J in LDS)
-#ifndef QPGPU_WAVE_KUDZ
-#define QPGPU_WAVE_KUDZ 8
-#endif
-constexpr int kUG = 8, kUL = QPGPU_WAVE_KUL;
+constexpr int kUG = 8, kUL = 4;
+constexpr int kUJ = 4;   // J columns of a Givens sweep loaded per chunk (LDS-resident J)
+constexpr int kUDZ = 8;  // chunk of compute_d_z's LDS sums (J in LDS)
 
 // Value of v held by lane i of this thread's subgroup (S = 16 / 32: lane i of each 16- / 32-lane group of the wave
 // serve the two QPs; S = 64: lane i).  i must be wave-uniform (a compile-time step index): two
@@ -173,15 +174,11 @@ __device__ __forceinline__ void sg_argmin(double& v, int& i) {
 // already gives up the reference's bits for north_star's 1e-10): update_r as a wave-wide tree
 // sum per row (no serial chain, no LDS round trip) and compute_d + update_z fused into one pass
 // over J (lane = row, column chunks tree-reduced), so J is read once per step instead of
-// 1 + (n - iq) / n times.  QPGPU_FLAG_EXACT keeps the serial, bit-exact sums.
+// 1 + (n - iq) / n times; add_constraint's J sweep deferred into the next d/z pass, two sweeps
+// deferred with J written back every second add.  QPGPU_FLAG_EXACT keeps the serial, bit-exact sums.
 // (Variants measured neutral or slower on C5 and removed in round 3, kept in git history:
 // coefficients loaded per chunk of rotations in the J sweep, two constraints per lane in the
 // l1 scan, the t1 selection across the four waves — DESIGN §5.3.)
-#ifndef QPGPU_WAVE_TOLLOOP
-#define QPGPU_WAVE_TOLLOOP 15  // bit 0: fused compute_d + update_z, bit 1: tree update_r,
-                               // bit 2: add_constraint J sweep deferred into the next d/z pass,
-                               // bit 3: two sweeps deferred, J written back every second add
-#endif
 // v from the lane the DPP control CTRL selects (a full-row permutation: every lane valid)
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
@@ -270,93 +267,43 @@ __device__ __forceinline__ double colsum16(double (&v)[16]) {
 // across the loop — C3 16.7 vs 15.4 ms, profiles/r02_s8 —, all of a lane's CI loads issued at
 // once in the scan — 16.0 vs 15.3 ms, profiles/r02_s10 —, and J in registers with packed R at
 // two waves per SIMD — C3 18.7 vs 14.5 ms, mgqp 1.96 vs 1.76 ms, profiles/r02_s19.)
-// four QPs per wave (S = 16) for n <= 16, m <= 32 (the mgqp hierarchy levels)
-#ifndef QPGPU_WAVE_S16
-#define QPGPU_WAVE_S16 1
-#endif
-#ifndef QPGPU_WAVE_FALLTHRU
-#define QPGPU_WAVE_FALLTHRU 1
-#endif
-#ifndef QPGPU_WAVE_RPACK
-#define QPGPU_WAVE_RPACK 1
-#endif
-#ifndef QPGPU_WAVE_REGSETUP
-#define QPGPU_WAVE_REGSETUP 1
-#endif
-// update_r on the lead with row i-1's row values and first chunk of its R and r entries loaded
-// while row i's division is in flight, r[i+1] carried in a register, later chunks double-buffered
-#ifndef QPGPU_WAVE_URPF
-#define QPGPU_WAVE_URPF 1
-#endif
-#ifndef QPGPU_WAVE_URU
-#define QPGPU_WAVE_URU 4
-#endif
-// the select after a scan prepared inside the scan (argmin, np gather, ci0[ip] in flight early)
-#ifndef QPGPU_WAVE_PRESEL
-#define QPGPU_WAVE_PRESEL 1
-#endif
+
+// Chunk sizes and occupancies of the loop (values that measurements settled; to try another, edit
+// the constant):
+constexpr int kURU = 4;       // R and r entries per chunk of the lead's prefetching update_r
+constexpr int kHCU = 8;       // rotations per unmasked chunk of add_constraint's |h| chain
+// CI loads per chunk of the two-constraint l1 scan (one global-memory round trip per chunk)
+constexpr int kScanKG = 16;
+constexpr int kScanKG4 = 16;  // the 128-VGPR (four waves per SIMD) instantiations
+// largest block LDS (bytes) for which the S < 64 variants launch their four-waves-per-SIMD
+// instantiation (128 VGPRs); larger blocks go to the OCC 2 / 1 ones
+constexpr int kOcc4Lds = 20480;
+constexpr int kOccSmall = 4;  // the waves per SIMD that instantiation is compiled for
+// waves per SIMD the workspace variant's registers are allocated for (128 VGPRs, four resident
+// QPs per CU)
+constexpr int kGjrOcc = 4;
 // per-phase clocks of the diagnostic stamps (tools/stamps_wave.py; off in the product build:
 // their accumulators cost ~50 VGPRs, which the l1 scan's 16-row chunks use instead)
 #ifndef QPGPU_WAVE_STAMPS
 #define QPGPU_WAVE_STAMPS 0
 #endif
-// add_constraint's |h| chain in unmasked chunks + a one-rotation tail, qp_distance_f
-#ifndef QPGPU_WAVE_HCHAIN2
-#define QPGPU_WAVE_HCHAIN2 1
-#endif
-#ifndef QPGPU_WAVE_HCU  // rotations per unmasked chunk of the |h| chain
-#define QPGPU_WAVE_HCU 8
-#endif
-// add_constraint's J sweep (J in LDS) in unmasked chunks + a one-rotation tail
-#ifndef QPGPU_WAVE_SWEEP2
-#define QPGPU_WAVE_SWEEP2 1
-#endif
-// CI loads per chunk of the two-constraint l1 scan (one global-memory round trip per chunk)
-#ifndef QPGPU_WAVE_SCANKG
-#define QPGPU_WAVE_SCANKG 16
-#endif
-#ifndef QPGPU_WAVE_SCANKG4  // the 128-VGPR (four waves per SIMD) instantiations
-#define QPGPU_WAVE_SCANKG4 16
-#endif
 // diagnostic stamps only: slots 5..7 hold, instead of the equality-phase parts, the loop's
 // update_r cycles, step count and sum of iq over steps (1), or add_constraint's |h| chain +
 // coefficients, J sweep and R column + test cycles, equality phase and loop together (2)
-// largest block LDS (bytes) for which the S < 64 variants launch their four-waves-per-SIMD
-// instantiation (128 VGPRs); A/B builds lower it to send such shapes to the OCC 2 / 1 ones
-#ifndef QPGPU_WAVE_OCC4_LDS
-#define QPGPU_WAVE_OCC4_LDS 20480
-#endif
-#ifndef QPGPU_WAVE_OCC_SMALL  // the waves per SIMD that instantiation is compiled for
-#define QPGPU_WAVE_OCC_SMALL 4
-#endif
-// waves per SIMD the workspace variant's registers are allocated for (4: 128 VGPRs, four resident
-// QPs per CU; an A/B build may lower it)
-#ifndef QPGPU_WAVE_GJR_OCC
-#define QPGPU_WAVE_GJR_OCC 4
-#endif
-#ifndef QPGPU_WAVE_GJR_CAP
-#define QPGPU_WAVE_GJR_CAP 0
-#endif
 #ifndef QPGPU_WAVE_STAMPS_DETAIL
 #define QPGPU_WAVE_STAMPS_DETAIL 0
 #endif
 // Tolerance-mode l1 scan from an fp32 copy of CI (the workspace variant, n > 64):
 // each s_i first from the half-size copy with a rigorous bound on its distance from the fp64
 // sum, then the exact fp64 sum only for the constraints the select can pick; a pass whose stop
-// test or candidates the bounds cannot settle scans in fp64 as before.  0 = always fp64.
-#ifndef QPGPU_WAVE_SHADOW
-#define QPGPU_WAVE_SHADOW 1
-#endif
+// test or candidates the bounds cannot settle scans in fp64 as before (and so does every pass
+// when the run-time hook qpk_set_shadow turns the copy off).
 constexpr int kShadowCand = 16;  // most exact re-evaluations per shadow scan (else the fp64 scan)
 // diagnostic counts (qpgpu_debug_shadow_stats): l1 scans that tried the fp32 copy, and those the
 // bounds settled (one atomic per QP and scan, by the lead)
 __device__ unsigned long long g_shadow_stats[3];  // [2]: fp64 re-evaluations (candidates)
-#ifndef QPGPU_WAVE_SHADOW_U  // fp32 CI loads per constraint and chunk of the shadow scan
-#define QPGPU_WAVE_SHADOW_U 32
-#endif
-#ifndef QPGPU_WAVE_SHADOW_KP  // a lane's constraints whose chunks load together
-#define QPGPU_WAVE_SHADOW_KP 1
-#endif
+constexpr int kShadowU = 32;  // fp32 CI loads per constraint and chunk of the shadow scan
+constexpr int kShadowKP = 1;  // a lane's constraints whose chunks load together
 // per-QP control block (lead lane writes, subgroup reads after grp_sync)
 struct Ctl {
   double f, t, t1, t2, ss, R_norm, c1, c2, psi, ci0ip, znp;
@@ -393,10 +340,7 @@ struct WaveCfg {
 // Vectors: x z d np r x_old (n each), the Givens coefficients (4n, interleaved per rotation),
 // u u_old (n+1 each), s (m), then int A A_old
 // (n+1 each), uint8 act exc (m each) and the control block.
-#ifndef QPGPU_WAVE_TOLCH
-#define QPGPU_WAVE_TOLCH 16
-#endif
-constexpr int kTolCh = QPGPU_WAVE_TOLCH;  // columns per tree-summed chunk of the tolerance-mode d/z pass
+constexpr int kTolCh = 16;  // columns per tree-summed chunk of the tolerance-mode d/z pass
 struct WaveLay {
   int js, nr, off_r, off_x, off_z, off_d, off_np, off_rv, off_xo, off_gc, off_u, off_uo, off_s,
       off_a, off_fl, off_ctl, off_tsc, off_sp, stride;
@@ -492,19 +436,17 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     else
       return false;
   };
-  constexpr bool kRegSetup = QPGPU_WAVE_REGSETUP && !GJR && NMAX <= S &&
-                             ((S == 32 && OCC == 1) || (S == 16 && OCC <= 2));
+  constexpr bool kRegSetup = !GJR && NMAX <= S && ((S == 32 && OCC == 1) || (S == 16 && OCC <= 2));
   // R packed (upper triangle + subdiagonal) with J still in LDS: less LDS per QP, more resident
   // blocks per CU (the register setup keeps the factor L in its own overlay)
-  constexpr bool kRPack = QPGPU_WAVE_RPACK && kRegSetup;
-  constexpr bool kPackedR = kRPack;
+  constexpr bool kPackedR = kRegSetup;
   // lane-parallel selections (argmin of s for l2, of u/r for t1) for one-wave subgroups
   constexpr bool kLaneSel = S <= 64;
   // loads in flight per lane in the global-operand sums (deeper for the one-QP-per-workgroup
   // workspace variant, whose lanes have registers to spare)
   constexpr int KG = GJR ? 16 : kUG;
   extern __shared__ double lds[];
-  const WaveLay Ly = wave_lay(a.n, a.m, GJR, kRPack);
+  const WaveLay Ly = wave_lay(a.n, a.m, GJR, kPackedR);
   const int JS = GJR ? BigWs<NMAX>::JS : Ly.js;
 
   const int tid = threadIdx.x;
@@ -885,7 +827,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   uint64_t tph[6] = {0, 0, 0, 0, 0, 0}, teq[5] = {0, 0, 0, 0, 0}, tdet[3] = {0, 0, 0};
   auto clk = [&]() -> uint64_t { return (QPGPU_WAVE_STAMPS && a.stamps) ? __builtin_amdgcn_s_memtime() : 0; };
   // iq0 of an add_constraint whose J sweep was deferred into the next d/z pass, or -1
-  // (tolerance mode, QPGPU_WAVE_TOLLOOP bit 2; the same value in every lane).  A QP can finish
+  // (tolerance mode; the same value in every lane).  A QP can finish
   // with a sweep still pending (no violated constraint after a successful add, or the step
   // cap): its J in the workspace is then not the reference's final J.  Nothing reads J after
   // the loop in this mode — J reaches the caller only through QPGPU_FLAG_WRITE_FACTOR (G, the
@@ -893,26 +835,25 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   // (defer needs `pre`, which only the panel setup sets).  A future J export from this path
   // must first apply the pending sweep (plain_sweep with iq0 = pend).
   int pend = -1;
-  constexpr bool kDefer = GJR && (QPGPU_WAVE_TOLLOOP & 4) && (QPGPU_WAVE_TOLLOOP & 1) && S == 4 * 64 && NMAX <= S;
-  // Two deferred sweeps (QPGPU_WAVE_TOLLOOP bit 3): the d/z pass after an add applies the
+  constexpr bool kDefer = GJR && S == 4 * 64 && NMAX <= S;
+  // Two sweeps are deferred: the d/z pass after an add applies the
   // pending sweep A in registers without writing J back; the next add's sweep B joins it and the
   // pass after that applies A then B (B one rotation behind A along each row) and writes the
   // final columns once — each trailing column of J is written once per two adds instead of once
   // per add.  While B is pending, A's coefficients sit in the workspace (gA) because B's occupy
   // gc.  pend2 = B's iq0 or -1; J in memory is current only with nothing pending, so
   // delete_constraint and a degenerate add first apply what is pending.
-  constexpr bool kDefer2 = kDefer && (QPGPU_WAVE_TOLLOOP & 8);
   int pend2 = -1;
   [[maybe_unused]] double* const gA = GJR ? Jm + BigWs<NMAX>::OFF_G : nullptr;
   auto compute_d_z = [&](int iq, [[maybe_unused]] int bip = -1) {  // bip: BOX, the loop's ip
     {
-      if constexpr (GJR && (QPGPU_WAVE_TOLLOOP & 1) && S == 4 * 64 && NMAX <= S) {
+      if constexpr (kDefer) {
         if (pre && n >= 2 * kTolCh) {  // the same test as add_constraint's defer
           // tolerance mode: lane r holds row r of each chunk of kDC columns (column-major J:
           // coalesced), d[c] = sum_r J[r][c] np[r] as per-wave tree sums + the four wave partials
           // in wave order (LDS, double-buffered), then z[r] += J[r][c] d[c] for c >= iq from the
           // same registers.  One pass over J.  With a deferred add_constraint sweep (pend = its
-          // iq0, QPGPU_WAVE_TOLLOOP bit 2) the pass applies the sweep too: columns below iq0 are
+          // iq0) the pass applies the sweep too: columns below iq0 are
           // read as they are, then each chunk of rotations produces its final columns n-1-g in
           // registers (stored back to J) and their d and z terms, and column iq0 gets the carry.
           constexpr int kDC = kTolCh;
@@ -950,7 +891,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
             for (int u = 0; u < kDC; u++) jv[u] = (row && c0 + u < cA) ? J_(ls, c0 + u) : 0.0;
             chunk(jv, [&](int u) { return c0 + u < cA ? c0 + u : -1; });
           }
-          if (kDefer2 && ps >= 0 && pend2 >= 0) {
+          if (ps >= 0 && pend2 >= 0) {
             // A (coefficients in gA, rotations g = 0..ngA-1 on columns (n-2-g, n-1-g)) then B
             // (gc, pend2 = ps + 1, one rotation fewer): A's rotation g yields column n-1-g, which
             // is the t1 of B's rotation g-1 (g = 0: B's initial carry); B's rotation g-1 yields
@@ -997,9 +938,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
             chunk(cv, [&](int u) { return u == 0 ? ps + 1 : (u == 1 ? ps : -1); });
             pend = pend2 = -1;
           } else if (ps >= 0) {
-            // one pending sweep: applied in registers; with two-deep deferral it stays pending
-            // (J is not written back), otherwise its final columns are written now
-            const bool keep = kDefer2;
+            // one pending sweep: applied in registers; it stays pending (J is not written back)
             const int ng = ctl->ngiv;  // = n - 1 - ps
             double carry = row ? J_(ls, n - 1) : 0.0;
             for (int gb = 0; gb < ng; gb += kDC) {
@@ -1017,17 +956,14 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
                   const double n1 = t1 * c + t2 * sn;
                   fv[u] = f ? xn * (t1 + n1) - t2 : t2;
                   carry = f ? n1 : t1;
-                  if (row && !keep) J_(ls, n - 1 - g) = fv[u];
                 }
               }
               chunk(fv, [&](int u) { return gb + u < ng ? n - 1 - gb - u : -1; });
             }
-            if (row && !keep) J_(ls, ps) = carry;
             double cv[kDC];
 #pragma unroll
             for (int u = 0; u < kDC; u++) cv[u] = u == 0 ? carry : 0.0;
             chunk(cv, [&](int u) { return u == 0 ? ps : -1; });
-            if (!keep) pend = -1;
           }
           if (row) zv[ls] = z;
           grp_sync<S>();
@@ -1044,12 +980,12 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       } else {  // (body left at its indentation)
       for (int c = ls; c < n; c += S)
         dv[c] = GJR ? seq_fma_up<KG>(0.0, 0, n, [&](int j) { return J_(j, c); }, [&](int j) { return npv[j]; })
-                    : seq_fma_up_lds<QPGPU_WAVE_KUDZ>(0.0, 0, n, [&](int j) { return J_(j, c); }, [&](int j) { return npv[j]; });
+                    : seq_fma_up_lds<kUDZ>(0.0, 0, n, [&](int j) { return J_(j, c); }, [&](int j) { return npv[j]; });
       }
       grp_sync<S>();
       for (int r = ls; r < n; r += S)
         zv[r] = GJR ? seq_fma_up<KG>(0.0, iq, n, [&](int j) { return J_(r, j); }, [&](int j) { return dv[j]; })
-                    : seq_fma_up_lds<QPGPU_WAVE_KUDZ>(0.0, iq, n, [&](int j) { return J_(r, j); }, [&](int j) { return dv[j]; });
+                    : seq_fma_up_lds<kUDZ>(0.0, iq, n, [&](int j) { return J_(r, j); }, [&](int j) { return dv[j]; });
       grp_sync<S>();
     }
   };
@@ -1063,7 +999,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   // dual step's drop and the rollback use the inequalities' u; x and f never use u), and r[i]
   // for i >= p does not depend on the rows below.
   auto update_r = [&](int iq, int lo) {
-    if constexpr (!GJR && QPGPU_WAVE_URPF) {
+    if constexpr (!GJR) {
       // row i: s = R[i][i+1] r[i+1] + sum_{j >= i+2} R[i][j] r[j] in j order (the reference's
       // order: +0.0 first, then each product).  r[i+1] stays in a register (no LDS round trip on
       // the chain); the next row's loads (R[i-1][i-1..i+U], d[i-1], r[i+1..i+U]) are
@@ -1073,7 +1009,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       // s is never -0.0 (it starts at +0.0 and a sum is -0.0 only from two -0.0 operands), so
       // adding +0.0 leaves it unchanged.
       if (lead && iq > lo) {
-        constexpr int U = QPGPU_WAVE_URU;
+        constexpr int U = kURU;
         auto rowp = [&](int i) -> const double* {
           return kPackedR ? Rm + (i * n - (i * (i - 1)) / 2 - i) : Rm + i * JS;
         };
@@ -1154,65 +1090,54 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         for (; i >= lo && iq - i - 2 < U; i--) row(i, std::false_type{});
         for (; i >= lo; i--) row(i, std::true_type{});
       }
-    } else if constexpr (!GJR) {
-      if (lead)
-        for (int i = iq - 1; i >= lo; i--) {
-          // row i of R as a pointer (Ri[j] = R[i][j], j >= i): packed rows are contiguous too
-          const double* Ri = kPackedR ? Rm + (i * n - (i * (i - 1)) / 2 - i) : Rm + i * JS;
-          const double s = seq_fma_up<kUL>(0.0, i + 1, iq, [&](int j) { return Ri[j]; },
-                                      [&](int j) { return rv[j]; });
-          rv[i] = wdiv<F>(dv[i] - s, Ri[i], fok);
-        }
     } else {
       if (ls >= 64) return;  // waves 1.. idle (they wait at the caller's grp_sync)
       constexpr int PU = (NMAX + 63) / 64;
-      if constexpr (QPGPU_WAVE_TOLLOOP & 2) {
-        if (pre) {
-          // tolerance mode: lane l holds r[j] for j = l + 64u in registers; row i's products
-          // R[i][j] r[j] (j in (i, iq)) are summed by the wave's tree (wave_sum_f64), so each row
-          // costs a tree sum and a division.  Rows are fetched kRD ahead (a register ring with
-          // compile-time slots) so the global loads' latency is off the chain.
-          constexpr int kRD = 4;
-          double rr[PU], ring[kRD][PU], rd[kRD], rg[kRD];
+      if (pre) {
+        // tolerance mode: lane l holds r[j] for j = l + 64u in registers; row i's products
+        // R[i][j] r[j] (j in (i, iq)) are summed by the wave's tree (wave_sum_f64), so each row
+        // costs a tree sum and a division.  Rows are fetched kRD ahead (a register ring with
+        // compile-time slots) so the global loads' latency is off the chain.
+        constexpr int kRD = 4;
+        double rr[PU], ring[kRD][PU], rd[kRD], rg[kRD];
 #pragma unroll
-          for (int u = 0; u < PU; u++) rr[u] = 0.0;
-          auto fetch_row = [&](int i, double* dst, double& di, double& gi) {
+        for (int u = 0; u < PU; u++) rr[u] = 0.0;
+        auto fetch_row = [&](int i, double* dst, double& di, double& gi) {
+#pragma unroll
+          for (int u = 0; u < PU; u++) {
+            const int j = ls + 64 * u;
+            dst[u] = (i >= 0 && j > i && j < iq) ? R_(i, j) : 0.0;
+          }
+          di = i >= 0 ? dv[i] : 0.0;
+          gi = i >= 0 ? R_(i, i) : 1.0;
+        };
+#pragma unroll
+        for (int k = 0; k < kRD; k++) fetch_row(iq - 1 - k, ring[k], rd[k], rg[k]);
+        for (int i0 = iq - 1; i0 >= lo; i0 -= kRD) {
+#pragma unroll
+          for (int k = 0; k < kRD; k++) {
+            const int i = i0 - k;
+            if (i < lo) break;
+            double rc[PU];
+#pragma unroll
+            for (int u = 0; u < PU; u++) rc[u] = ring[k][u];
+            const double di = rd[k], gi = rg[k];
+            fetch_row(i - kRD, ring[k], rd[k], rg[k]);
+            double sl = 0.0;
 #pragma unroll
             for (int u = 0; u < PU; u++) {
               const int j = ls + 64 * u;
-              dst[u] = (i >= 0 && j > i && j < iq) ? R_(i, j) : 0.0;
+              sl += (j > i && j < iq) ? rc[u] * rr[u] : 0.0;
             }
-            di = i >= 0 ? dv[i] : 0.0;
-            gi = i >= 0 ? R_(i, i) : 1.0;
-          };
+            const double ri = (di - wave_sum_f64(sl)) / gi;
 #pragma unroll
-          for (int k = 0; k < kRD; k++) fetch_row(iq - 1 - k, ring[k], rd[k], rg[k]);
-          for (int i0 = iq - 1; i0 >= lo; i0 -= kRD) {
-#pragma unroll
-            for (int k = 0; k < kRD; k++) {
-              const int i = i0 - k;
-              if (i < lo) break;
-              double rc[PU];
-#pragma unroll
-              for (int u = 0; u < PU; u++) rc[u] = ring[k][u];
-              const double di = rd[k], gi = rg[k];
-              fetch_row(i - kRD, ring[k], rd[k], rg[k]);
-              double sl = 0.0;
-#pragma unroll
-              for (int u = 0; u < PU; u++) {
-                const int j = ls + 64 * u;
-                sl += (j > i && j < iq) ? rc[u] * rr[u] : 0.0;
-              }
-              const double ri = (di - wave_sum_f64(sl)) / gi;
-#pragma unroll
-              for (int u = 0; u < PU; u++)
-                if (ls + 64 * u == i) rr[u] = ri;
-              if (lead) rv[i] = ri;
-            }
+            for (int u = 0; u < PU; u++)
+              if (ls + 64 * u == i) rr[u] = ri;
+            if (lead) rv[i] = ri;
           }
-          sg_sync();
-          return;
         }
+        sg_sync();
+        return;
       }
       double* const P = gc;  // scratch (the Givens buffers are free during a step)
       double rn[PU], rc[PU];
@@ -1382,7 +1307,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   };
   auto add_constraint = [&]() {
     const uint64_t h0 = clk();
-    if constexpr (kDefer2) {
+    if constexpr (kDefer) {
       // a sweep is pending (its coefficients in gc): they move to the workspace before this
       // add's rotations are recorded in gc
       if (pend >= 0) {
@@ -1395,12 +1320,12 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     if (lead && !hp) {
       const int iq = ctl->iq;
       int ng = 0;
-      if (QPGPU_WAVE_HCHAIN2 && iq < n) {
+      if (iq < n) {
         // full chunks of U rotations without per-rotation exec-mask branches (the chunk's d
         // values loaded together), then the tail one rotation per trip; distance() with the
         // range-reduced sqrt (qp_common.h)
         double carried = dv[n - 1];
-        constexpr int U = QPGPU_WAVE_HCU;
+        constexpr int U = kHCU;
         int jb = n - 1;
         for (; jb - U >= iq; jb -= U) {
           double ac[U];
@@ -1425,25 +1350,6 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
           GX_(ng) = h;
           carried = skip ? a0 : h;
           ng++;
-        }
-      } else if (iq < n) {
-        double carried = dv[n - 1];
-        constexpr int U = 8;  // d values of a chunk loaded together, ahead of the h chain
-        for (int jb = n - 1; jb >= iq + 1; jb -= U) {
-          double ac[U];
-#pragma unroll
-          for (int u = 0; u < U; u++) ac[u] = jb - u >= iq + 1 ? dv[jb - u - 1] : 0.0;
-#pragma unroll
-          for (int u = 0; u < U; u++)
-            if (jb - u >= iq + 1) {
-              const double a0 = ac[u];
-              const double h = wdist<F>(a0, carried, fok);
-              const bool skip = fabs(h) < kEps;
-              GF_(ng) = skip ? 0.0 : 1.0;
-              GX_(ng) = h;
-              carried = skip ? a0 : h;
-              ng++;
-            }
         }
       }
       ctl->ngiv = ng;
@@ -1489,60 +1395,40 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     // constraint turns out degenerate (then delete_constraint needs the swept J right away)
     const bool defer = kDefer && pre && n >= 2 * kTolCh;
     auto plain_sweep = [&]() {
-      // Row k's sweep over columns n-1 .. iq: rotation g maps (J[k][j-1], J[k][j]), j = n-1-g,
-      // to (n1, xny (t1 + n1) - t2) and n1 is the next rotation's t2, so it is carried in a
-      // register and the t1 loads (independent of the chain) are issued kU at a time.
-      constexpr bool kGC = false;  // (coefficients per chunk in the workspace variant: removed)
-      constexpr int kU = GJR ? KG : QPGPU_WAVE_KUJ;
+      // The workspace variant's sweep (with J in LDS the chunked one below runs instead).  Row
+      // k's sweep over columns n-1 .. iq: rotation g maps (J[k][j-1], J[k][j]), j = n-1-g, to
+      // (n1, xny (t1 + n1) - t2) and n1 is the next rotation's t2, so it is carried in a
+      // register and the t1 loads (independent of the chain) are issued KG at a time; the
+      // coefficients are read per rotation (registers: the variant's occupancy).
       const int ng = ctl->ngiv;
       for (int k = ls; k < n; k += S) {
         double carry = J_(k, n - 1);
-        for (int gb = 0; gb < ng; gb += kU) {
-          // the chunk's J entries (and, with J in LDS, its rotation coefficients) are loaded
-          // before its first store (LDS stores would otherwise fence every later load); the
-          // workspace variant reads the coefficients per rotation (registers: its occupancy)
-          constexpr int kUC = (GJR && !kGC) ? 1 : kU;
-          double t1v[kU], cv[kUC], sw[kUC], xw[kUC];
-          bool fw[kUC];
+        for (int gb = 0; gb < ng; gb += KG) {
+          double t1v[KG];
 #pragma unroll
-          for (int u = 0; u < kU; u++) {
-            const int g = gb + u;
-            const bool ok = g < ng;
-            t1v[u] = ok ? J_(k, n - 2 - g) : 0.0;
-            if constexpr (!GJR || kGC) {
-              cv[u] = ok ? GC_(g) : 0.0;
-              sw[u] = ok ? GS_(g) : 0.0;
-              xw[u] = ok ? GX_(g) : 0.0;
-              fw[u] = ok && GF_(g) != 0.0;
-            }
-          }
+          for (int u = 0; u < KG; u++) t1v[u] = gb + u < ng ? J_(k, n - 2 - gb - u) : 0.0;
 #pragma unroll
-          for (int u = 0; u < kU; u++) {
+          for (int u = 0; u < KG; u++) {
             const int g = gb + u;
             if (g < ng) {
-              const int uc = (GJR && !kGC) ? 0 : u;
-              if constexpr (GJR && !kGC) {
-                cv[0] = GC_(g);
-                sw[0] = GS_(g);
-                xw[0] = GX_(g);
-                fw[0] = GF_(g) != 0.0;
-              }
+              const double cv = GC_(g), sw = GS_(g), xw = GX_(g);
+              const bool fw = GF_(g) != 0.0;
               const double t1 = t1v[u], t2 = carry;
-              const double n1 = t1 * cv[uc] + t2 * sw[uc];
+              const double n1 = t1 * cv + t2 * sw;
               // skipped step (gf = 0): both columns unchanged
-              J_(k, n - 1 - g) = fw[uc] ? xw[uc] * (t1 + n1) - t2 : t2;
-              carry = fw[uc] ? n1 : t1;
+              J_(k, n - 1 - g) = fw ? xw * (t1 + n1) - t2 : t2;
+              carry = fw ? n1 : t1;
             }
           }
         }
         J_(k, n - 1 - ng) = carry;
       }
     };
-    if (!GJR && QPGPU_WAVE_SWEEP2 && iq0 < n) {
+    if (!GJR && iq0 < n) {
       // the sweep below with J in LDS: full chunks of kU rotations with no per-rotation
       // exec-mask branch (the chunk's J entries and coefficients loaded first), then the tail
       // one rotation per trip
-      constexpr int kU = QPGPU_WAVE_KUJ;
+      constexpr int kU = kUJ;
       const int ng = ctl->ngiv;
       for (int k = ls; k < n; k += S) {
         double carry = J_(k, n - 1);
@@ -1604,14 +1490,14 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     grp_sync<S>();
     if (defer && iq0 < n) {
       if (ctl->fin) {
-        if (kDefer2 && pend >= 0)
+        if (pend >= 0)
           pend2 = iq0;  // = pend + 1: the d/z pass applies both and writes J back
         else
           pend = iq0;
       } else {
         // degenerate: delete_constraint needs the current J — the pending sweep (its
         // coefficients now in gA), then this one
-        if (kDefer2 && pend >= 0) {
+        if (pend >= 0) {
           sweep_coef(gA, n - 1 - pend);
           grp_sync<S>();
           pend = -1;
@@ -1626,7 +1512,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   // R re-triangularisation (recording the rotations), the lanes shift R's rows and rotate
   // J's columns.
   auto delete_constraint = [&](int l) {
-    if constexpr (kDefer2) {
+    if constexpr (kDefer) {
       // J must be current: a sweep kept pending by the last d/z pass (its coefficients still in
       // gc: no add since) is applied now
       if (pend >= 0) {
@@ -1705,7 +1591,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     {
       // row k's sweep over columns qq .. qq+ng: rotation g maps (J[k][j], J[k][j+1]), j = qq+g,
       // to (n1, xny (n1 + t1) - t2); the second is the next rotation's t1 (carried)
-      constexpr int kU = GJR ? KG : QPGPU_WAVE_KUJ;
+      constexpr int kU = GJR ? KG : kUJ;
       const int ng = ctl->ngiv, qq = ctl->qq;
       for (int k = ls; k < n; k += S) {
         double carry = J_(k, qq);
@@ -1839,7 +1725,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     grp_sync<S>();
   }
   // ------------------------------------------------------------------ active-set loop
-  // ---- the tolerance-mode l1 scan from the fp32 copy of CI (QPGPU_WAVE_SHADOW; workspace
+  // ---- the tolerance-mode l1 scan from the fp32 copy of CI (workspace
   // variant).  Each lane's s~_i = fl(sum_j (double)CI32[j][i] x_j) + ci0_i in j order, with a bound
   // B_i >= |s_i - s~_i| for the fp64 scan's s_i: CI32 = CI (1 + d), |d| <= 2^-24, or |CI32 - CI|
   // <= 2^-126 below fp32's normal range, and both sums' rounding (each <= (n + 1) eps' of
@@ -1858,7 +1744,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   // The candidates get their fp64 s_i (the same products and the same j-order sum as the fp64
   // scan: the lanes form the n products, the lead adds them) into sv; the other sv entries keep
   // s~_i.  Otherwise (false) the caller scans in fp64, overwriting sv.
-  constexpr bool kShadow = !BOX && GJR && QPGPU_WAVE_SHADOW && S == 4 * 64 && NMAX <= S;
+  constexpr bool kShadow = !BOX && GJR && S == 4 * 64 && NMAX <= S;
   bool shadow_hit = false;
   [[maybe_unused]] auto shadow_scan = [&]() -> bool {
     constexpr int KS = (MMAX + S - 1) / S;  // constraints per lane
@@ -1871,7 +1757,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     double lpsi = 0.0, le = 0.0, les = 0.0;
     bool lbad = false;
     // KP of a lane's constraints per pass over j (their loads of a chunk in flight together)
-    constexpr int KP = QPGPU_WAVE_SHADOW_KP < KS ? QPGPU_WAVE_SHADOW_KP : KS;
+    constexpr int KP = kShadowKP < KS ? kShadowKP : KS;
     static_assert(KS % KP == 0, "constraints per lane in whole groups");
 #pragma unroll
     for (int k0 = 0; k0 < KS; k0 += KP) {
@@ -1884,7 +1770,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
           Aa[q] = 0.0;
           ia[q] = ls + (k0 + q) * S < m ? ls + (k0 + q) * S : m - 1;  // (a clamped one is discarded)
         }
-        constexpr int U = QPGPU_WAVE_SHADOW_U;
+        constexpr int U = kShadowU;
         for (int jb = 0; jb < n; jb += U) {
           float c[KP][U];
 #pragma unroll
@@ -2035,11 +1921,11 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   const int max_steps = a.max_steps;
   // the select that follows a scan (carried ss reset to 0): its argmin, the np gather and
   // ci0[ip] are started inside the scan, so their global loads overlap the lead's psi sum
-  constexpr bool kPreSel = QPGPU_WAVE_PRESEL && kLaneSel && !GJR && MMAX <= 2 * S && NMAX <= S;
+  constexpr bool kPreSel = kLaneSel && !GJR && MMAX <= 2 * S && NMAX <= S;
   [[maybe_unused]] double pre_sb = 0.0, pre_np = 0.0, pre_c0 = 0.0;
   [[maybe_unused]] int pre_ib = INT_MAX;
   [[maybe_unused]] bool from_scan = false;
-  // A QP falls through scan -> select -> step within one pass of the loop (QPGPU_WAVE_FALLTHRU),
+  // A QP falls through scan -> select -> step within one pass of the loop,
   // so two QPs of a wave at different phases share the later blocks instead of running them in
   // separate passes.
   while (true) {
@@ -2075,7 +1961,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
         const bool h0 = i0 < m, h1 = i1 < m;
         const int c0i = h0 ? i0 : 0, c1i = h1 ? i1 : c0i;
         const double c00 = BOX ? box_b(c0i) : EL(ci0b, c0i), c01 = BOX ? box_b(c1i) : EL(ci0b, c1i);
-        constexpr int SKG = OCC >= 4 ? QPGPU_WAVE_SCANKG4 : QPGPU_WAVE_SCANKG;
+        constexpr int SKG = OCC >= 4 ? kScanKG4 : kScanKG;
         double s0 = 0.0, s1 = 0.0;
         int jb = 0;
         if constexpr (BOX) {  // (m = 2n >= 2: c0i and c1i are constraints of this QP)
@@ -2208,7 +2094,6 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       for (int i = ls; i < n; i += S) xo[i] = xv[i];
       grp_sync<S>();
       tph[0] += clk() - t0;
-      if (!QPGPU_WAVE_FALLTHRU) continue;
       phase = ctl->phase;
     }
     if (phase == PH_SELECT) {
@@ -2330,7 +2215,6 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       }
       from_scan = false;
       tph[1] += clk() - t0;
-      if (!QPGPU_WAVE_FALLTHRU) continue;
       phase = ctl->phase;
     }
     if (phase != PH_STEP) continue;
@@ -2587,7 +2471,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
 }
 
 template <int S, int NMAX, int MMAX, bool GJR, int OCC = 1>
-__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : OCC)
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : OCC)
     QP_WAVE_KERNEL(const QpArgs a, double* __restrict__ ws) {
   if constexpr (GJR) {
     // the EXACT re-solve after a tolerance-mode launch: only the QPs marked for it (one QP per
@@ -2611,19 +2495,19 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : O
 // qpgpu_solve_batched_dual: a kernel of its own (one per variant, the OCC = 1 layout), so the
 // kernels above are the same code as without it
 template <int S, int NMAX, int MMAX, bool GJR>
-__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : 1)
     qp_wave_dual_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, true>(a, ws);
 }
 // qpgpu_solve_batched_box: likewise a kernel of its own per variant, the OCC = 1 layout
 template <int S, int NMAX, int MMAX, bool GJR>
-__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : 1)
     qp_wave_box_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, false, true>(a, ws);
 }
 // qpgpu_solve_batched_box_dual: bounds and the multipliers, again a kernel of its own per variant
 template <int S, int NMAX, int MMAX, bool GJR>
-__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? QPGPU_WAVE_GJR_OCC : 1)
+__global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : 1)
     qp_wave_box_dual_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, true, true>(a, ws);
 }
@@ -2659,7 +2543,7 @@ template <int S, int NMAX, int MMAX, bool GJR>
 static hipError_t launch_wave_mode(WaveKernel kernel, const QpArgs& a, hipStream_t stream, double* ws) {
   using C = WaveCfg<S, NMAX, MMAX, GJR>;
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  const bool rpack = S < 64 && !GJR && QPGPU_WAVE_RPACK != 0;
+  const bool rpack = S < 64 && !GJR;
   const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
   if (lds_bytes > 65536) {
     const hipError_t e = grant_dynamic_lds(kernel, lds_bytes);
@@ -2698,14 +2582,14 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   // instantiation compiled for 4 waves per SIMD (a few spilled VGPRs).  Measured: mgqp level 0
   // (10.5 KiB per block) 2.44 -> 2.32 ms; C3 (37 KiB per block, LDS-limited to one wave per SIMD)
   // keeps the unconstrained allocation (21.0 vs 22.0 ms).  The register-setup instantiations
-  // (OCC 2 for S = 16, OCC 1) use the packed-R layout when QPGPU_WAVE_RPACK is on.
+  // (OCC 2 for S = 16, OCC 1) use the packed-R layout.
   if constexpr (S < 64 && !GJR) {
-    if (lds_bytes <= QPGPU_WAVE_OCC4_LDS) {
-      hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, QPGPU_WAVE_OCC_SMALL>), dim3((unsigned)blocks), dim3(C::BS),
+    if (lds_bytes <= kOcc4Lds) {
+      hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, kOccSmall>), dim3((unsigned)blocks), dim3(C::BS),
                          lds_bytes, stream, a, ws);
       return hipGetLastError();
     }
-    const size_t lds_p = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, QPGPU_WAVE_RPACK != 0).stride * sizeof(double);
+    const size_t lds_p = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, true).stride * sizeof(double);
     // four-QP waves (S = 16): up to 40 KiB per block still leaves room for two waves per SIMD
     if (S == 16 && lds_bytes <= 40960) {
       hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, 2>), dim3((unsigned)blocks), dim3(C::BS),
@@ -2713,14 +2597,6 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
       return hipGetLastError();
     }
     lds_bytes = lds_p;  // OCC 1 (register setup) from here on
-  }
-  // workspace variant (n > 64): an A/B build with -DQPGPU_WAVE_GJR_CAP=k pads the dynamic LDS so
-  // at most k one-QP workgroups share a CU (fewer resident QPs = a working set that may stay in
-  // the Infinity Cache).  The product build has no cap.
-  if constexpr (GJR && QPGPU_WAVE_GJR_CAP > 0) {
-    constexpr size_t cap = QPGPU_WAVE_GJR_CAP > 0 ? QPGPU_WAVE_GJR_CAP : 1;
-    const size_t want = (size_t)163840 / cap - 1024;
-    if (want > lds_bytes) lds_bytes = want;
   }
   if (lds_bytes > 65536) {
     const hipError_t e = grant_dynamic_lds(QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>, lds_bytes);
@@ -2744,9 +2620,8 @@ struct WaveVariant {
 #define QPK_WAVE_NAMES(plain, s) {plain "qp_wave<" s ">", "qp_wave_dual<" s ">", "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"}
 #endif
 static const WaveVariant kWaveVariants[] = {
-#if QPGPU_WAVE_S16
+    // four QPs per wave (S = 16) for n <= 16, m <= 32 (the mgqp hierarchy levels)
     {16, 32, 0, QPK_WAVE_NAMES("", "S=16,N=16,M=32"), launch_wave<16, 16, 32, false>},
-#endif
     {32, 64, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=64"), launch_wave<32, 32, 64, false>},
     {32, 128, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=128"), launch_wave<32, 32, 128, false>},
     {64, 128, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=128"), launch_wave<64, 64, 128, false>},
@@ -2797,10 +2672,10 @@ static bool uses_panel(const qpk::WaveVariant* v, uint32_t flags) {
   return v->ws_doubles_per_qp > 0 && !(flags & (QPGPU_FLAG_EXACT | QPGPU_FLAG_WRITE_FACTOR));
 }
 
-// The fp32 copy of CI for the tolerance-mode shadow scan (QPGPU_WAVE_SHADOW): QP-major batches
+// The fp32 copy of CI for the tolerance-mode shadow scan: QP-major batches
 // of the panel path, after the batch's per-QP workspace blocks, up to 16 GiB (a larger batch
 // scans in fp64).  qpk_set_shadow(0) (qpgpu_debug_set_shadow) turns it off for A/B tests.
-static bool g_shadow = QPGPU_WAVE_SHADOW != 0;
+static bool g_shadow = true;
 static int64_t shadow_bytes(const qpk::WaveVariant* v, const qpk::QpArgs* a) {
   if (!g_shadow || !uses_panel(v, a->flags) || a->tile != 1 || a->m <= 0) return 0;
   const int64_t b = (int64_t)a->n * a->m * 4 * a->batch;
@@ -2849,7 +2724,7 @@ extern "C" hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream
 // the status words and skips the EXACT re-solve
 extern "C" void qpk_set_resolve(int on) { g_resolve = on != 0; }
 // test / diagnostic hook (qpgpu_debug_set_shadow): 0 scans in fp64 only
-extern "C" void qpk_set_shadow(int on) { g_shadow = on != 0 && QPGPU_WAVE_SHADOW != 0; }
+extern "C" void qpk_set_shadow(int on) { g_shadow = on != 0; }
 // diagnostic (qpgpu_debug_shadow_stats): out[0] scans that tried the fp32 copy, out[1] those it
 // settled, out[2] the fp64 re-evaluations of candidates they made, since the last reset;
 // device-synchronous

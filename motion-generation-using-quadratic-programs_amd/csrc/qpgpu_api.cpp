@@ -257,34 +257,6 @@ static qpk::QpArgs make_args(const qpgpu_problem_desc* d, double* G, const doubl
   return a;
 }
 
-// QPs [b0, b0 + count) of a's batch: every per-QP pointer advanced to QP b0's block in a's layout
-// (TILED64: b0 a multiple of 64, so a whole-tile boundary), NULL left NULL.
-static qpk::QpArgs sub_range(const qpk::QpArgs& a, int64_t b0, int64_t count) {
-  const int64_t n = a.n, p = a.p, m = a.m;
-  const auto blocks = [&](auto* q, int64_t E) { return q ? q + (a.tile == 64 ? b0 / 64 * 64 * E : b0 * E) : q; };
-  const auto each = [&](auto* q) { return q ? q + b0 : q; };
-  qpk::QpArgs c = a;
-  c.batch = count;
-  c.G = blocks(a.G, n * n);
-  c.g0 = blocks(a.g0, n);
-  c.CE = blocks(a.CE, n * p);
-  c.ce0 = blocks(a.ce0, p);
-  c.CI = blocks(a.CI, n * m);
-  c.ci0 = blocks(a.ci0, m);
-  c.x = blocks(a.x, n);
-  c.f = each(a.f);
-  c.status = each(a.status);
-  c.iters = each(a.iters);
-  c.x_eq = blocks(a.x_eq, n);
-  c.f_eq = each(a.f_eq);
-  c.st_eq = each(a.st_eq);
-  c.u = blocks(a.u, p + m);
-  c.nact = each(a.nact);
-  c.hi = blocks(a.hi, n);
-  c.lo = blocks(a.lo, n);
-  return c;
-}
-
 // The generic kernel's workspace is per QP (2n^2 + 12n + 2m doubles): a large shape launches
 // over sub-batches whose workspace stays within g_generic_ws_cap (one allocation reused by every
 // sub-batch in stream order), instead of one allocation for the whole batch — n = 2000 over
@@ -302,7 +274,7 @@ static int launch_generic(const qpk::QpArgs& a, hipStream_t s, std::unique_lock<
   const int rc = device_workspace(per * (chunk < a.batch ? chunk : a.batch), s, &ws, ws_hold);
   if (rc) return rc;
   for (int64_t b0 = 0; b0 < a.batch; b0 += chunk) {
-    qpk::QpArgs c = sub_range(a, b0, a.batch - b0 < chunk ? a.batch - b0 : chunk);
+    qpk::QpArgs c = qpk::sub_range(a, b0, a.batch - b0 < chunk ? a.batch - b0 : chunk);
     if (c.hi) c.CI = c.ci0 = c.g0;  // (never read; kept inside an array of this sub-batch)
     c.stamps = nullptr;
     const hipError_t e = qpk_launch_generic(&c, s, ws);
@@ -829,7 +801,7 @@ int qpgpu_solve_batched_multi(const qpgpu_problem_desc* d, int32_t ndev, const i
     if (cnt <= 0) continue;
     qpgpu_problem_desc dk = *d;
     dk.batch = cnt;
-    const qpk::QpArgs c = sub_range(all, lo[k], cnt);
+    const qpk::QpArgs c = qpk::sub_range(all, lo[k], cnt);
     const int dev = devices[k];
     g_pool[k]->submit([=]() -> int {
       hipError_t e = hipSetDevice(dev);

@@ -1,9 +1,13 @@
 #!/bin/bash
-# Build an A/B variant of libqpgpu.so with extra -D flags for one kernel source (SRC, default
-# qp_lane; the other objects are the in-tree build's) into _ab/<name>/libqpgpu.so; register /
-# scratch figures of that source's kernels go to _ab/<name>/regs.txt.
-# SRCFILE overrides the source text (e.g. an earlier revision: git show REV:path > file).
-#   usage: [SRC=qp_wave] [SRCFILE=path] tools/ab_build.sh NAME -DFLAG=V ...
+# Build an A/B variant of libqpgpu.so from one kernel source (SRC, default qp_lane; the other
+# objects are the in-tree build's) into _ab/<name>/libqpgpu.so; register / scratch figures of
+# that source's kernels go to _ab/<name>/regs.txt.  A side is
+#   * a -D of a switch the source still has (the diagnostic builds: -DQPGPU_WAVE_STAMPS=1,
+#     -DQPGPU_WAVE_STAMPS_DETAIL=1|2, -DQPGPU_LANE_STAMPS=0|2), or
+#   * SRCFILE=path, another revision of the source text (git show REV:path > file) — the settled
+#     strategy switches are folded into the sources, their other sides are in history (DESIGN
+#     §5.15 names the last commit that has each; a -D of a retired name fails the compile).
+#   usage: [SRC=qp_wave] [SRCFILE=path] tools/ab_build.sh NAME [-DFLAG=V ...]
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -29,7 +33,10 @@ MK
 )
 # the fast lane build is the same source with QPGPU_LANE_FAST (qp_lane_fast.hip) and contraction
 XF=""; case "$SRC" in qp_lane_fast|qp_lane_fast_u|qp_wave_fast) XF="-ffp-contract=fast";; esac
-for f in qp_layout qp_lane qp_lane_p0 qp_lane_fast qp_lane_u qp_lane_fast_u qp_small qp_wave qp_wave_fast qp_panel qp_generic qpgpu_api; do [ "$f" = "$SRC" ] || cp "$PKG/lib/$f.o" "$OUT/"; done
+# every object the Makefile links into lib/libqpgpu.so (its prerequisites, from make's database)
+OBJS=$(make -s -C "$PKG" --no-print-directory -pqn lib/libqpgpu.so 2>/dev/null | sed -n 's/^lib\/libqpgpu\.so: //p')
+[ -n "$OBJS" ] || { echo "ab_build: no prerequisites of lib/libqpgpu.so in the Makefile" >&2; exit 1; }
+for o in $OBJS; do [ "$o" = "lib/$SRC.o" ] || cp "$PKG/$o" "$OUT/"; done
 (cd "$OUT/tmp" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math -fPIC \
    -std=c++17 -I"$ROOT/include" -I"$PKG/csrc" $SCHED $DEFS $XF "$@" -c "${SRCFILE:-$PKG/csrc/$SRC.hip}" -o "$OUT/$SRC.o" -save-temps 2>&1 | grep -v warning | grep -v "warnings\? generated" || true)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libqpgpu.so" "$OUT"/*.o
