@@ -942,6 +942,10 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // updates start at p.
   constexpr int IQLO = PX >= 0 ? (PX <= NM ? PX : NM) : 0;
   const auto kLo = std::integral_constant<int, IQLO>{};
+  // One free dimension (the full-wave kernel of a shape with p = n - 1: C1 / C4's (7, 6, 14)): the
+  // active set holds at most one inequality, and the loop pass below the scan is a
+  // two-state machine over a handful of scalars, instead of the general select and step.
+  constexpr bool kOneFree = FULL && PX >= 0 && PX == NM - 1;
   {
     double sv[MM];
 #pragma unroll
@@ -1005,9 +1009,11 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
           double psi = 0.0;
           if (do_scan) {
             iter++;
+            if constexpr (!kOneFree) {  // (the one-free pass forms the mask from its one slot)
 #pragma unroll
             for (int k = 0; k < NM; k++)
               if (k >= p && k < iq) act |= 1ull << Av[k];
+            }
 #pragma unroll
             for (int i = 0; i < MM; i++) sv[i] = 0.0;
           }
@@ -1136,7 +1142,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
             ip = 0;
             if (fabs(psi) <= (double)m * kEps * c1 * c2 * 100.0) {
               active = false;  // optimal
-            } else {
+            } else if constexpr (!kOneFree) {  // (the one-free pass copies x under its select's loads)
 #pragma unroll
               for (int i = 0; i < NM; i++) {
                 if (i < IQLO || i < iq) {
@@ -1163,6 +1169,136 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         if (nloop == 0) tfirst = tl1 - tl0;
       }
       nloop++;
+      // kOneFree: select and step of one pass, the general ones below restated for n - p = 1.  Then
+      // iq is S = n - 1 or S + 1, and of the general machinery only this is ever reached:
+      //   * add_constraint and delete_constraint rotate nothing (their Givens loops run over j >= S + 1
+      //     and over an empty range), so J is the equality phase's for the whole loop, and only its
+      //     column S is read: d[S] = J[:,S] . np, and z = J[:,S] d[S] while slot S is empty;
+      //   * the only entry of R that is read is R[S][S] (r[S] = d[S] / R[S][S]), written by the add;
+      //   * with slot S empty (iq = S) no inequality can be dropped, t1 = inf: the step is the full
+      //     step to constraint ip or, without a finite t2, infeasible; t = t2 exactly, so the partial
+      //     step and its refresh of s[ip] never occur, s is the scan's, and s[ip] is the select's ss
+      //     (ss < 0 whenever a step runs, and no pass moves ip without moving ss to s[ip]);
+      //   * with slot S taken (iq = S + 1) z sums over an empty range: z = 0, zz = 0, t2 = inf, and the
+      //     step is infeasible or the dual step that drops slot S, after which the pending constraint
+      //     ip and its multiplier 0.0 + t (u[S + 1] is the select's 0.0 there) move into the slot and
+      //     the same ip is stepped to without a scan or a select;
+      //   * a failed add leaves iq = S, so the rollback restores x alone; the slot's A and u are
+      //     rewritten by the select that follows.  ss and ip keep their values through it (no
+      //     eligible s[i] is below the old minimum), as in the general loop.
+      // State: iq, A[S] (the constraint in the slot; read only while iq = S + 1), u[S], R[S][S],
+      // R_norm, x, f, ip, ss, np, excl and xold.  Every floating-point value comes from the general
+      // loop's operations in their order (sums ascending from 0.0, the 0.0 + starts kept).
+      if constexpr (kOneFree) {
+        constexpr int S = NM - 1;
+        constexpr int RSS = RI::at(S, S);
+        // ---- l2: the most violated constraint not in the slot and not excluded
+        if (active && need_select) {
+          const uint32_t blocked = (uint32_t)excl | (iq > S ? 1u << Av[S] : 0u);
+#pragma unroll
+          for (int i = 0; i < MM; i++) {
+            const bool take = sv[i] < ss && !((blocked >> i) & 1u);
+            ss = take ? sv[i] : ss;
+            ip = take ? i : ip;
+          }
+          if (ss >= 0.0) {
+            active = false;  // optimal
+          } else {
+#pragma unroll
+            for (int j = 0; j < NM; j++)
+              npv[j] = (j < kCiRows && ci_ready) ? ci_lds_at(j * MM + ip) : ldCI(j * m + ip);
+            // (ci0[ip] is not loaded: only the partial step's refresh reads it)
+            // the rollback copy, under the loads: x is the scan's here, or the x a rollback restored
+#pragma unroll
+            for (int i = 0; i < NM; i++) xold[i] = xv[i];
+            if (iq == S) uv[S] = 0.0;  // (u[S + 1] = 0.0 is implied, A[iq] = ip is the slot's at the add)
+          }
+        }
+        if (kStamps && a.stamps) {
+          const double sink = npv[0] + npv[NM - 1];  // the select's loads are part of its span
+          asm volatile("" ::"v"(sink));
+          tsel += __builtin_amdgcn_s_memtime() - tl1;
+        }
+        // ---- l2a
+        if (active) {
+          if (max_steps > 0 && ++steps > max_steps) {
+            status = QPGPU_QP_MAX_ITER;
+            active = false;
+          } else {
+            [[maybe_unused]] uint64_t ts0 = 0;
+            if constexpr (QPGPU_LANE_STAMPS == 2) ts0 = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
+            const bool has = iq > S;  // slot S holds an inequality
+            double dS = 0.0;
+#pragma unroll
+            for (int j = 0; j < NM; j++) dS += Jreg[j][S] * npv[j];
+            double rS = 0.0;
+            if (has) {
+              rS = ldiv<F>(dS - 0.0, Rv[RSS], fok);
+            } else {
+#pragma unroll
+              for (int r = 0; r < NM; r++) zv[r] = 0.0 + Jreg[r][S] * dS;
+            }
+            if constexpr (QPGPU_LANE_STAMPS == 2) {
+              if (a.stamps) {
+                const double sink = rS + zv[0] + dS;
+                asm volatile("" ::"v"(sink));
+                tdzr += __builtin_amdgcn_s_memtime() - ts0;
+              }
+            }
+            if (has) {
+              // t2 = inf, t = t1 = u[S] / r[S] where r[S] > 0 and the quotient is below inf
+              double t1 = inf;
+              if (rS > 0.0) {
+                const double q_ = ldiv<F>(uv[S], rS, fok);
+                t1 = (q_ < t1) ? q_ : t1;
+              }
+              if (t1 >= inf) {
+                status = QPGPU_QP_INFEASIBLE;
+                fval = inf;
+                active = false;
+              } else {  // dual step: slot S is dropped, the pending constraint takes it
+                uv[S] = 0.0 + t1;
+                iq = S;
+                need_scan = need_select = false;
+              }
+            } else {
+              const double zz = dot(zv, zv);
+              const double znp = dot(zv, npv);
+              double t2 = inf;
+              if (fabs(zz) > kEps) {
+                t2 = ldiv<F>(-ss, znp, fok);
+                if (t2 < 0) t2 = inf;  // Takano Akio patch
+              }
+              if (!(t2 < inf)) {  // t = t1 = inf
+                status = QPGPU_QP_INFEASIBLE;
+                fval = inf;
+                active = false;
+              } else {  // full step (t = t2), then the add
+                const double t = t2;
+#pragma unroll
+                for (int k = 0; k < NM; k++) xv[k] += t * zv[k];
+                fval += t * znp * (0.5 * t + uv[S]);
+                uv[S] = uv[S] + t;
+                const double dd = fabs(dS);
+                if (dd <= kEps * R_norm) {  // degenerate: roll back to the l1 state, select again
+                  excl = (uint32_t)excl | (1u << ip);
+#pragma unroll
+                  for (int i = 0; i < NM; i++) xv[i] = xold[i];
+                  need_scan = false;
+                  need_select = true;
+                } else {
+                  R_norm = (R_norm < dd) ? dd : R_norm;
+                  Rv[RSS] = dS;
+                  Av[S] = ip;
+                  iq = S + 1;
+                  need_scan = need_select = true;
+                }
+              }
+            }
+          }
+        }
+        continue;
+      }
       // ---- l2: pick the most violated constraint (ss deliberately not reset: reference quirk)
       if (active && need_select) {
         if constexpr (BOX) {
