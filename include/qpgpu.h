@@ -396,7 +396,8 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d,
  * input).
  *
  * Shapes: n <= 64 with any p and any m (n*n, n*p and n*m below 2^31).  n > 64 is
- * QPGPU_ERR_UNSUPPORTED_SHAPE (it needs a workspace or a blocked factorisation).  d->max_iter is
+ * QPGPU_ERR_UNSUPPORTED_SHAPE here: L, M and S of one QP no longer fit on chip, and qpgpu_vjp_ws
+ * below serves 64 < n <= 256 from a workspace the caller provides.  d->max_iter is
  * ignored; d->flags must be 0.  Decided before any array is read, QPGPU_ERR_INVALID_ARGUMENT:
  * non-zero flags; a NULL u with p + m > 0; with batch > 0 a NULL G, x or gx, a NULL CE with p > 0, a
  * NULL CI with m > 0.  batch = 0 is QPGPU_SUCCESS.  status may be NULL: every QP is evaluated.  With
@@ -453,6 +454,60 @@ int qpgpu_vjp_box(const qpgpu_problem_desc* d,
  * "lane" (one QP per lane) for n <= 8, "group" (one QP per 16, 32 or 64 lanes) for 8 < n <= 64,
  * "" for n > 64 or n <= 0. */
 const char* qpgpu_kernel_name_vjp(int32_t n, int32_t p, int32_t m);
+
+/* ---- the backward step with a caller's workspace: n <= 256 ------------------------------------------
+ * qpgpu_vjp_ws and qpgpu_vjp_box_ws are qpgpu_vjp and qpgpu_vjp_box with two more arguments, a
+ * workspace in device memory and its size.  Everything said at qpgpu_vjp and qpgpu_vjp_box holds
+ * unless stated here: the mathematics and the definition, bit for bit; both layouts, natural
+ * alignment and sub-ranges; NULL outputs; status masking to +0.0 and q > n giving NaN; d->flags
+ * must be 0 and d->max_iter is ignored; the argument rules and their order, all decided before any
+ * array is read or anything is launched.
+ *
+ * Shapes.  n <= 64 runs exactly the launch qpgpu_vjp makes: the same kernel, the same bits; the
+ * workspace is not touched and may be NULL with workspace_bytes 0.  64 < n <= 256 with any p and
+ * any m (n*p and n*m below 2^31) runs the workspace kernel, one workgroup of 256 lanes per QP in
+ * flight.  Not built: n > 256 is QPGPU_ERR_UNSUPPORTED_SHAPE (the kernel gives a row of L, and of
+ * S, to a lane of one workgroup).
+ *
+ * Workspace.  One QP in flight occupies a slot of
+ *     per_qp(n, p, m) = 8 * (3*n*n + n) bytes for 64 < n <= 256,   0 for n <= 64
+ * (a multiple of 8; p and m do not enter): L (n x n), M with gx as an extra column (n x (n+1)) and
+ * S, then R, (n x n); the short vectors and the working list stay on chip.
+ * qpgpu_vjp_workspace_bytes writes slots * per_qp to *bytes: QPGPU_ERR_INVALID_ARGUMENT for
+ * slots < 1, a NULL bytes, a NULL d or d->n <= 0 (or a negative p, m or batch);
+ * QPGPU_ERR_UNSUPPORTED_SHAPE for n > 256.  The entry uses
+ *     slots = min(batch, workspace_bytes / per_qp)
+ * of them: one resident workgroup per slot, workgroup s walking the QPs s, s + slots, ...  For
+ * n > 64 and batch > 0, decided after the rules above and before the device is touched, each of a
+ * NULL workspace, a workspace that is not 8-byte aligned and a workspace with room for less than
+ * one slot is QPGPU_ERR_INVALID_ARGUMENT.  The workspace's contents on entry do not matter and its
+ * contents afterwards are unspecified; the call writes nothing outside
+ * [workspace, workspace + slots * per_qp) and its own QPs' requested gradients.  THE RESULTS DO NOT
+ * DEPEND ON THE NUMBER OF SLOTS, only the time does.  Calls on one stream may share a workspace
+ * (they run in stream order); concurrent streams need one each.
+ *
+ * The call only enqueues: it allocates nothing and synchronises nothing, so the first call for a
+ * shape can be captured into a hipGraph, with the workspace the caller's like every other array. */
+int qpgpu_vjp_workspace_bytes(const qpgpu_problem_desc* d, int64_t slots, int64_t* bytes);
+
+int qpgpu_vjp_ws(const qpgpu_problem_desc* d,
+                 const double* G, const double* CE, const double* CI,
+                 const double* x, const double* u, const int32_t* status,
+                 const double* gx,
+                 double* dG, double* dg0, double* dCE, double* dce0, double* dCI, double* dci0,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
+int qpgpu_vjp_box_ws(const qpgpu_problem_desc* d,
+                     const double* G, const double* CE,
+                     const double* x, const double* u, const int32_t* status,
+                     const double* gx,
+                     double* dG, double* dg0, double* dCE, double* dce0, double* dhi, double* dlo,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Name of the kernel a qpgpu_vjp_ws / qpgpu_vjp_box_ws launch of this shape runs:
+ * qpgpu_kernel_name_vjp's for n <= 64, a name containing "ws" for 64 < n <= 256, "" for n > 256 or
+ * n <= 0. */
+const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t p, int32_t m);
 
 /* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each

@@ -36,3 +36,13 @@ extern "C" const char* qpk_vjp_name(int n);
 // Enqueue the backward step of QPs [0, a->batch) on `stream`; tiled != 0: QPGPU_LAYOUT_TILED64.
 // n outside [1, 64] is hipErrorInvalidValue.
 extern "C" hipError_t qpk_launch_vjp(const qpk::VjpArgs* a, int tiled, hipStream_t stream);
+
+// qp_vjp_ws.hip, 64 < n <= 256 (include/qpgpu.h qpgpu_vjp_ws / qpgpu_vjp_box_ws).
+// The kernel a launch of this n runs: NULL for n outside [65, 256].
+extern "C" const char* qpk_vjp_ws_name(int n);
+// Doubles of workspace per QP in flight (a slot): 3 n^2 + n; 0 for n outside [65, 256].
+extern "C" int64_t qpk_vjp_ws_doubles(int n);
+// Enqueue the backward step of QPs [0, a->batch) on `stream`: min(slots, a->batch) workgroups, workgroup
+// s working in ws[s * doubles, (s + 1) * doubles) on the QPs s, s + slots, ...  n outside [65, 256], a
+// NULL ws or slots < 1 is hipErrorInvalidValue.
+extern "C" hipError_t qpk_launch_vjp_ws(const qpk::VjpArgs* a, int tiled, void* ws, int64_t slots, hipStream_t stream);

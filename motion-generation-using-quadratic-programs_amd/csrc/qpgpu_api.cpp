@@ -478,10 +478,9 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d, const double* G, const 
 // ---- the backward step (include/qpgpu.h; kernels: qp_vjp.hip) -------------------------
 // Both entries: every rule is decided from the descriptor and the pointers' values, before any
 // array is read; no workspace, one kernel, so the first call for a shape can be captured.
-static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
-                   const double* CI, const double* x, const double* u, const int32_t* status,
-                   const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
-                   double* dci0, double* dhi, double* dlo, void* stream) {
+// The argument rules of all four entries, in the header's order.
+static int vjp_rules(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                     const double* CI, const double* x, const double* u, const double* gx) {
   if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
   if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
   if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
@@ -494,11 +493,23 @@ static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const
     if (d->p > 0 && !CE) return QPGPU_ERR_INVALID_ARGUMENT;
     if (!box && d->m > 0 && !CI) return QPGPU_ERR_INVALID_ARGUMENT;
   }
-  // n <= 64: L, M and S of a QP fit on chip; a per-QP block is indexed with 32 bits
+  return QPGPU_SUCCESS;
+}
+
+// a per-QP block is indexed with 32 bits
+static bool vjp_sizes_fit(const qpgpu_problem_desc* d) {
   const int64_t lim = (int64_t)1 << 31;
-  if (!qpk_vjp_name(d->n) || (int64_t)d->n * d->m >= lim || (int64_t)d->n * d->p >= lim ||
-      (int64_t)d->p + d->m >= lim)
-    return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  return (int64_t)d->n * d->m < lim && (int64_t)d->n * d->p < lim && (int64_t)d->p + d->m < lim;
+}
+
+static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                   const double* CI, const double* x, const double* u, const int32_t* status,
+                   const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
+                   double* dci0, double* dhi, double* dlo, void* stream) {
+  const int rc = vjp_rules(d, box, G, CE, CI, x, u, gx);
+  if (rc) return rc;
+  // n <= 64: L, M and S of a QP fit on chip
+  if (!qpk_vjp_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   if (d->batch == 0) return QPGPU_SUCCESS;
   qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
                     dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
@@ -524,6 +535,66 @@ const char* qpgpu_kernel_name_vjp(int32_t n, int32_t p, int32_t m) {
   (void)p;
   (void)m;
   const char* k = qpk_vjp_name(n);
+  return k ? k : "";
+}
+
+// ---- the backward step with a caller's workspace (kernel for 64 < n <= 256: qp_vjp_ws.hip) --------
+// n <= 64 is vjp_run itself.  Beyond, the workspace rules follow the shape rule, all before the
+// device is touched; the launch allocates nothing, so the first call for a shape can be captured.
+static int vjp_ws_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                      const double* CI, const double* x, const double* u, const int32_t* status,
+                      const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
+                      double* dci0, double* dhi, double* dlo, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  const int rc = vjp_rules(d, box, G, CE, CI, x, u, gx);
+  if (rc) return rc;
+  if (qpk_vjp_name(d->n))
+    return vjp_run(d, box, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, dhi, dlo, stream);
+  if (!qpk_vjp_ws_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  if (d->batch == 0) return QPGPU_SUCCESS;
+  const int64_t per = qpk_vjp_ws_doubles(d->n) * (int64_t)sizeof(double);
+  if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < per)
+    return QPGPU_ERR_INVALID_ARGUMENT;
+  qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
+                    dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
+                    box ? dlo : nullptr};
+  const hipError_t e = qpk_launch_vjp_ws(&a, d->layout == QPGPU_LAYOUT_TILED64, workspace, workspace_bytes / per,
+                                         reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_vjp_workspace_bytes(const qpgpu_problem_desc* d, int64_t slots, int64_t* bytes) {
+  if (!d || !bytes || slots < 1) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->n > 64 && !qpk_vjp_ws_name(d->n)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  const int64_t per = qpk_vjp_ws_doubles(d->n) * (int64_t)sizeof(double);
+  if (per > 0 && slots > INT64_MAX / per) return QPGPU_ERR_INVALID_ARGUMENT;
+  *bytes = slots * per;
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_vjp_ws(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* CI,
+                 const double* x, const double* u, const int32_t* status, const double* gx, double* dG,
+                 double* dg0, double* dCE, double* dce0, double* dCI, double* dci0, void* workspace,
+                 int64_t workspace_bytes, void* stream) {
+  return vjp_ws_run(d, false, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, nullptr, nullptr,
+                    workspace, workspace_bytes, stream);
+}
+
+int qpgpu_vjp_box_ws(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* x,
+                     const double* u, const int32_t* status, const double* gx, double* dG, double* dg0,
+                     double* dCE, double* dce0, double* dhi, double* dlo, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  return vjp_ws_run(d, true, G, CE, nullptr, x, u, status, gx, dG, dg0, dCE, dce0, nullptr, nullptr, dhi, dlo,
+                    workspace, workspace_bytes, stream);
+}
+
+const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t p, int32_t m) {
+  (void)p;
+  (void)m;
+  const char* k = qpk_vjp_name(n);
+  if (!k) k = qpk_vjp_ws_name(n);
   return k ? k : "";
 }
 

@@ -74,6 +74,10 @@ EXPORTED_SYMBOLS = (
     "qpgpu_vjp",
     "qpgpu_vjp_box",
     "qpgpu_kernel_name_vjp",
+    "qpgpu_vjp_workspace_bytes",
+    "qpgpu_vjp_ws",
+    "qpgpu_vjp_box_ws",
+    "qpgpu_kernel_name_vjp_ws",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -134,6 +138,14 @@ def _load():
     lib.qpgpu_vjp_box.restype = ctypes.c_int
     lib.qpgpu_kernel_name_vjp.argtypes = [ctypes.c_int32] * 3
     lib.qpgpu_kernel_name_vjp.restype = ctypes.c_char_p
+    lib.qpgpu_vjp_workspace_bytes.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    lib.qpgpu_vjp_workspace_bytes.restype = ctypes.c_int
+    lib.qpgpu_vjp_ws.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13 + [vp, ctypes.c_int64, vp]
+    lib.qpgpu_vjp_ws.restype = ctypes.c_int
+    lib.qpgpu_vjp_box_ws.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 12 + [vp, ctypes.c_int64, vp]
+    lib.qpgpu_vjp_box_ws.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_vjp_ws.argtypes = [ctypes.c_int32] * 3
+    lib.qpgpu_kernel_name_vjp_ws.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -205,6 +217,32 @@ def kernel_name_vjp(n: int, p: int = 0, m: int = 0) -> str:
     """The kernel a qpgpu_vjp / qpgpu_vjp_box launch of this shape runs: a "lane" name for n <= 8, a
     "group" name for 8 < n <= 64, "" beyond (QPGPU_ERR_UNSUPPORTED_SHAPE)."""
     return LIB.qpgpu_kernel_name_vjp(n, p, m).decode()
+
+
+VJP_ON_CHIP_N = 64  # qpgpu_vjp / qpgpu_vjp_box stop here; beyond, the _ws entries take a workspace
+VJP_SLOTS = 512     # QPs in flight of a backward step with a workspace, unless the caller says
+
+
+def kernel_name_vjp_ws(n: int, p: int = 0, m: int = 0) -> str:
+    """The kernel a qpgpu_vjp_ws / qpgpu_vjp_box_ws launch of this shape runs: kernel_name_vjp's for
+    n <= 64, a "ws" name for 64 < n <= 256, "" beyond (QPGPU_ERR_UNSUPPORTED_SHAPE)."""
+    return LIB.qpgpu_kernel_name_vjp_ws(n, p, m).decode()
+
+
+def vjp_workspace_bytes(n: int, p: int, m: int, slots: int) -> int:
+    """qpgpu_vjp_workspace_bytes: the workspace of `slots` QPs in flight (0 for n <= 64)."""
+    d = ProblemDesc(n, p, m, 0, 0, 0, 0)
+    out = ctypes.c_int64(0)
+    _check(LIB.qpgpu_vjp_workspace_bytes(ctypes.byref(d), slots, ctypes.byref(out)), "qpgpu_vjp_workspace_bytes")
+    return out.value
+
+
+def _vjp_workspace(n, p, m, batch, slots, device):
+    """The uint8 workspace tensor of min(batch, slots) slots, from torch's caching allocator (so it
+    is ordered on the current stream like every other tensor)."""
+    import torch
+
+    return torch.empty(vjp_workspace_bytes(n, p, m, max(1, min(batch, slots))), dtype=torch.uint8, device=device)
 
 
 # the n > 64 default path's certification (DESIGN §3.4): a QP whose decisions the tolerance mode
@@ -550,7 +588,7 @@ class _DeviceBatchBase:
         n, p, m = self.n, self.p, self.m
         return {"dG": n * n, "dg0": n, "dCE": n * p, "dce0": p, "dCI": n * m, "dci0": m, "dhi": n, "dlo": n}[name]
 
-    def vjp(self, u, gx, outs=None, status=True, stream=None, x=None):
+    def vjp(self, u, gx, outs=None, status=True, stream=None, x=None, slots=VJP_SLOTS, workspace=None):
         """Enqueue the backward step (qpgpu_vjp / qpgpu_vjp_box, include/qpgpu.h) of this batch's
         resident inputs at (x, u) for gx = dl/dx on `stream` (default current): no host round
         trip, so it can follow a dual solve on the same stream.  u as kkt_residuals() takes it; gx:
@@ -560,7 +598,9 @@ class _DeviceBatchBase:
         a dict from output name (dG, dg0, dCE, dce0 and dCI, dci0 or dhi, dlo) to the tensor to
         write, or True to allocate it: an output that is not named is passed as NULL and not
         computed.  Returns the dict of the tensors written, each (rows, E) in this batch's layout
-        (vjp_rows() decodes host copies)."""
+        (vjp_rows() decodes host copies).  For n > 64 the call goes to qpgpu_vjp_ws /
+        qpgpu_vjp_box_ws with `workspace` (a uint8 tensor; default: a new one of min(batch, slots)
+        slots, which the results do not depend on); for n <= 64 both are ignored."""
         import torch
 
         x = self.x if x is None else x
@@ -577,8 +617,16 @@ class _DeviceBatchBase:
         d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
         vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         tensors = [getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st, gx] + [outs.get(k) for k in self._VJP_OUTPUTS]
-        _check(getattr(LIB, self._ENTRY_VJP)(ctypes.byref(d), *[vp(t) for t in tensors],
-                                             ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_VJP)
+        if self.n <= VJP_ON_CHIP_N:
+            _check(getattr(LIB, self._ENTRY_VJP)(ctypes.byref(d), *[vp(t) for t in tensors],
+                                                 ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_VJP)
+            return outs
+        entry = self._ENTRY_VJP + "_ws"
+        if workspace is None:
+            with torch.cuda.stream(stream):
+                workspace = _vjp_workspace(self.n, self.p, self.m, self.batch, slots, x.device)
+        _check(getattr(LIB, entry)(ctypes.byref(d), *[vp(t) for t in tensors], vp(workspace), workspace.numel(),
+                                   ctypes.c_void_p(stream.cuda_stream)), entry)
         return outs
 
     def vjp_rows(self, outs):
@@ -757,14 +805,15 @@ def kkt_residuals(pr, x, u, status=None, layout=None, device="cuda:0"):
     return db.kkt_rows(r)
 
 
-def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None):
+def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slots=VJP_SLOTS):
     """The gradients of l with respect to the data of every QP of `pr` (Problems: qpgpu_vjp;
     BoxProblems: qpgpu_vjp_box) at the primal-dual pair (x, u) for gx = dl/dx, computed on the GPU:
     a dict of float64 arrays shaped like the inputs — dG (B, n, n), dg0 (B, n), dCE (B, n, p),
     dce0 (B, p) and dCI (B, n, m), dci0 (B, m), or dhi, dlo (B, n) for bounds (include/qpgpu.h).
     x and gx are (B, n), u is (B, p + m) in QP-major order (may be None when p + m == 0); with
     `status` (B int32) a QP that is not QP_OK gets +0.0 everywhere.  outs: the names to compute
-    (default all six).  layout="tiled64" runs the TILED64 form (converted here on the host)."""
+    (default all six).  layout="tiled64" runs the TILED64 form (converted here on the host).  For
+    n > 64 the entries are qpgpu_vjp_ws / qpgpu_vjp_box_ws with a workspace of min(B, slots) slots."""
     import torch
 
     db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
@@ -775,7 +824,7 @@ def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None):
     xd, gd = up(x, pr.n), up(gx, pr.n)
     ud = up(u, E) if E > 0 else None
     sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
-    res = db.vjp(ud, gd, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd)
+    res = db.vjp(ud, gd, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd, slots=slots)
     torch.cuda.synchronize(xd.device)
     return db.vjp_rows(res)
 
@@ -818,13 +867,15 @@ def _layer_functions():
         vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(G.device).cuda_stream)
         gx = gx.contiguous()
-        if box:
-            rc = LIB.qpgpu_vjp_box(ctypes.byref(d), vp(G), vp(CE), vp(x), vp(u), vp(st), vp(gx),
-                                   *[vp(t) for t in outs], stream)
-        else:
-            rc = LIB.qpgpu_vjp(ctypes.byref(d), vp(G), vp(CE), vp(c5), vp(x), vp(u), vp(st), vp(gx),
-                               *[vp(t) for t in outs], stream)
-        _check(rc, "qpgpu_vjp_box" if box else "qpgpu_vjp")
+        ins = (vp(G), vp(CE)) + (() if box else (vp(c5),)) + (vp(x), vp(u), vp(st), vp(gx))
+        entry = "qpgpu_vjp_box" if box else "qpgpu_vjp"
+        if n <= VJP_ON_CHIP_N:
+            rc = getattr(LIB, entry)(ctypes.byref(d), *ins, *[vp(t) for t in outs], stream)
+        else:  # the workspace: torch's caching allocator, on the current stream
+            entry += "_ws"
+            ws = _vjp_workspace(n, p, m, B, VJP_SLOTS, G.device)
+            rc = getattr(LIB, entry)(ctypes.byref(d), *ins, *[vp(t) for t in outs], vp(ws), ws.numel(), stream)
+        _check(rc, entry)
         return tuple(outs)
 
     class QpLayer(torch.autograd.Function):
@@ -852,7 +903,8 @@ def qp_layer(G, g0, CE, ce0, CI, ci0):
     """The batched QP as a differentiable layer: x* (B, n) of
         min 0.5 x^T G x + g0^T x   s.t.  CE^T x + ce0 = 0,  CI^T x + ci0 >= 0
     for float64 device tensors G (B, n, n), g0 (B, n), CE (B, n, p), ce0 (B, p), CI (B, n, m),
-    ci0 (B, m), QP-major.  Forward is qpgpu_solve_batched_dual, backward qpgpu_vjp on the current
+    ci0 (B, m), QP-major.  Forward is qpgpu_solve_batched_dual, backward qpgpu_vjp (n > 64:
+    qpgpu_vjp_ws, its workspace from torch's caching allocator) on the current
     stream with no host round trip; an input that does not require grad gets none (its gradient
     is not computed), and no gradient flows through a QP whose status is not QP_OK (+0.0; its x is
     whatever the solve left: zeros for a G that is not positive definite)."""

@@ -13,7 +13,14 @@ first.  Prints one JSON line per shape and layout: median / min / max ms, the ra
 medians, and the bytes moved by the backward step (read: G, CE, x, u, gx, status and the working
 columns of CI; written: the six gradients, dCI's zero columns included).
 
+The n > 64 shapes (C5, ws100, ws65) go through qpgpu_vjp_ws.  Its workspace is allocated before
+anything is timed, one per slot count of --slots (default 512, the Python mirror's, then half and
+double that): the record's vjp_ms is the first count's, vjp_ms_by_slots has every count's, timed
+under the same protocol.
+
     python tools/vjp_cost.py [--reps 20] [--parent-lib PATH] [--out profiles/vjp_cost/vjp_cost.log]
+    python tools/vjp_cost.py --shapes C5,ws100,ws65 --layouts qp_major --parent-lib PATH \
+        --out profiles/vjp_ws_cost/vjp_ws_cost.log
 """
 import argparse
 import ctypes
@@ -29,7 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "motion-generation-using-quadratic-program
 
 MALL_BYTES = 256 << 20
 SHAPES = {"C1": (7, 6, 14, 65536), "C2": (8, 0, 16, 65536), "mgqp": (14, 10, 28, 65536),
-          "C3": (30, 6, 60, 16384), "n64": (64, 0, 128, 2048)}
+          "C3": (30, 6, 60, 16384), "n64": (64, 0, 128, 2048),
+          "C5": (256, 0, 512, 4096), "ws100": (100, 20, 200, 4096), "ws65": (65, 2, 130, 16384)}
 INPUTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
 
 
@@ -44,6 +52,7 @@ def main():
     ap.add_argument("--shapes", default="C1,C3")
     ap.add_argument("--layouts", default="qp_major,tiled64")
     ap.add_argument("--parent-lib", default=None, help="a libqpgpu.so of the parent commit for the dual solve")
+    ap.add_argument("--slots", default="512,256,1024", help="n > 64: QPs in flight, the first is the headline")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -92,9 +101,14 @@ def main():
                 rc = solve_lib.qpgpu_solve_batched_dual(*sets[q % R].solve_args[1])
                 assert rc == 0, rc
 
+            slot_counts = [int(v) for v in args.slots.split(",")] if n > qpgpu.VJP_ON_CHIP_N else [0]
+            spaces = {k: torch.empty(qpgpu.vjp_workspace_bytes(n, p, m, k), dtype=torch.uint8, device=dev)
+                      for k in slot_counts if k}
+            slots_now = [slot_counts[0]]
+
             def vjp(q):
                 db = sets[q % R]
-                db.vjp(db.u, db.gx, outs=db.grads, stream=s)
+                db.vjp(db.u, db.gx, outs=db.grads, stream=s, workspace=spaces.get(slots_now[0]))
 
             def timed(fn, q):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -119,6 +133,19 @@ def main():
                 ms["vjp"].append(timed(vjp, q))
                 ms["solve"].append(timed(solve, q))
             st = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+            by_slots = {str(slot_counts[0]): st(ms["vjp"])} if spaces else None
+            for k in slot_counts[1:]:
+                slots_now[0] = k
+                for w in range(2):  # untimed
+                    q += 1
+                    vjp(q)
+                torch.cuda.synchronize()
+                v = []
+                for w in range(args.reps):
+                    q += 1
+                    v.append(timed(vjp, q))
+                by_slots[str(k)] = st(v)
+            slots_now[0] = slot_counts[0]
             db = sets[0]
             uh = db.u.cpu().numpy().reshape(-1)
             uh = qpgpu.from_tiled64(uh, B, (p + m,)) if layout == "tiled64" else uh.reshape(-1, p + m)[:B]
@@ -129,9 +156,9 @@ def main():
             g = db.vjp_rows(db.grads)
             tv = np.median(ms["vjp"]) * 1e-3
             rec = {"shape": name, "n": n, "p": p, "m": m, "batch": B, "layout": layout, "input_sets": R,
-                   "reps": args.reps, "vjp_kernel": qpgpu.kernel_name_vjp(n, p, m),
+                   "reps": args.reps, "vjp_kernel": qpgpu.kernel_name_vjp_ws(n, p, m),
                    "solve_kernel": qpgpu.kernel_name(n, p, m), "solve_lib": args.parent_lib or "under test",
-                   "vjp_ms": st(ms["vjp"]), "dual_solve_ms": st(ms["solve"]),
+                   "vjp_ms": st(ms["vjp"]), "vjp_ms_by_slots": by_slots, "dual_solve_ms": st(ms["solve"]),
                    "vjp_over_dual_solve": float(np.median(ms["vjp"]) / np.median(ms["solve"])),
                    "vjp_bytes_read": read, "vjp_bytes_written": written,
                    "vjp_GBps": (read + written) / tv * 1e-9,
@@ -141,7 +168,7 @@ def main():
                    "dual_solve_raw_ms": [round(v, 4) for v in ms["solve"]]}
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
-            del sets, base
+            del sets, base, spaces
             torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
