@@ -86,6 +86,11 @@ int mgqp_update_batched(mgqp_ctl* c, int64_t count, const mgqp_cycle_inputs* in,
 /* Device-resident batch: every pointer is DEVICE memory, robot-major
  * (robot r's block at r * block size).  NULL = RTT::NoData for all robots of the batch. */
 #define MGQP_MAX_DOF 16
+/* solver_flags bit (outside the QPGPU_FLAG_* bits, never passed on to the solver): the level QPs'
+ * Hessian is the identity and their linear term zero (reference src/mgqp.cpp:672-708), so solve
+ * them with qpgpu_solve_batched_unit: the cycle then neither initialises nor reads the identity
+ * matrices in its workspace.  Same outputs, bit for bit.  Not with QPGPU_FLAG_FAST (-1). */
+#define MGQP_SOLVER_UNIT_HESSIAN 0x10000u
 typedef struct {
   int64_t count;
   const float* angles;      /* [count][status_len] */
@@ -101,7 +106,8 @@ typedef struct {
   int32_t jac_cols[MGQP_MAX_DOF];
   int32_t status_len;
   uint32_t solver_flags; /* QPGPU_FLAG_* for the level solves: 0 (bitwise with the host paths) or
-                            QPGPU_FLAG_FAST (the wave kernel's fast build: within 1e-10) */
+                            QPGPU_FLAG_FAST (the wave kernel's fast build: within 1e-10); or
+                            MGQP_SOLVER_UNIT_HESSIAN (bitwise too, no identity G array) */
 } mgqp_device_batch;
 
 /* One control cycle for `b->count` robots entirely on the GPU: builder, per-level QPs, the

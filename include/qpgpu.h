@@ -303,6 +303,48 @@ int qpgpu_solve_batched_box_dual(const qpgpu_problem_desc* d,
  * (every such name contains "box" and "dual"); "" where qpgpu_kernel_name_box returns "". */
 const char* qpgpu_kernel_name_box_dual(int32_t n, int32_t p, uint32_t flags);
 
+/* The identity Hessian without a G array:
+ *     min 1/2 x^T x + g0^T x   s.t.   CE^T x + ce0 = 0,   CI^T x + ci0 >= 0,
+ * the Euclidean projection of -g0 onto a polytope, and the form of every QP the reference's
+ * controller solves (src/mgqp.cpp:672-708: JG = Identity, g0 = 0).  Device pointers, enqueue only,
+ * graph-capturable like qpgpu_solve_batched (no workspace: a first call can be captured); both
+ * layouts, natural alignment, sub-ranges of a larger batch; only the outputs of its own QPs are
+ * written.  x_eq, f_eq and status_eq are the m = 0 answers of qpgpu_solve_batched_eq: pass all
+ * three or none (a mixed triple is QPGPU_ERR_INVALID_ARGUMENT).
+ *
+ * The call is DEFINED as qpgpu_solve_batched with QPGPU_FLAG_EXACT (qpgpu_solve_batched_eq with
+ * the triple) on the same arrays and a materialised G = I.  The setup is stated, not computed:
+ *     J = I (1.0 on the diagonal, +0.0 elsewhere),   c1 = c2 = the ascending sum of n ones,
+ *     x0[i] = -g0[i] (IEEE negation),   f0 = 0.5 * sum_i g0[i] * x0[i] (ascending from +0.0, each
+ *     product rounded),   R_norm = 1,   iq = 0,
+ * and from there the reference's algorithm runs unchanged.  x, f, status and iters (and x_eq,
+ * f_eq, status_eq) are bit-identical to that dense solve, and so to the reference, on every QP
+ * whose g0 entries are all finite and none of which is -0.0: the dense setup forms
+ * g0[i] - (+0.0 * y[k]), which is g0[i] exactly unless y[k] is non-finite, and whose sign for
+ * g0[i] = -0.0 depends on the signs of the other entries.  The reference's own g0 = +0.0 is
+ * inside the contract; NaN, +-inf and -0.0 entries of g0 are outside it.
+ *
+ * QPGPU_FLAG_EXACT is accepted and implied.  QPGPU_FLAG_FAST (there is no fast unit form) and
+ * QPGPU_FLAG_WRITE_FACTOR (there is no G to write a factor into) are QPGPU_ERR_INVALID_ARGUMENT.
+ * With batch > 0 a NULL g0, x, f or status, a NULL CE or ce0 with p > 0 and a NULL CI or ci0 with
+ * m > 0 are QPGPU_ERR_INVALID_ARGUMENT; iters may be NULL; batch = 0 is QPGPU_SUCCESS.
+ * Shapes: n <= 64 and m <= 256 (the lane, subgroup and wave-LDS families); the default dispatch
+ * follows qpgpu_solve_batched's order for (n, p, m), and QPGPU_FLAG_FORCE_LANE / _SUBGROUP / _WAVE
+ * work as there.  n > 64, m > 256, QPGPU_FLAG_FORCE_GENERIC and a forced family that does not
+ * cover the shape are QPGPU_ERR_UNSUPPORTED_SHAPE. */
+int qpgpu_solve_batched_unit(const qpgpu_problem_desc* d,
+                             const double* g0,
+                             const double* CE, const double* ce0,
+                             const double* CI, const double* ci0,
+                             double* x, double* f, int32_t* status, int32_t* iters,
+                             double* x_eq, double* f_eq, int32_t* status_eq,
+                             void* stream);
+
+/* Name of the kernel a qpgpu_solve_batched_unit launch of shape (n, p, m) with these flags runs
+ * (every unit kernel's name contains "unit"); "" where the entry would refuse the flags or the
+ * shape. */
+const char* qpgpu_kernel_name_unit(int32_t n, int32_t p, int32_t m, uint32_t flags);
+
 /* ---- the KKT check: is (x, u) a solution of its QP? ---------------------------------------------
  * qpgpu_kkt_residuals evaluates, on the device, the optimality conditions of every QP of a batch
  * at a given primal-dual pair: QPGPU_KKT_NRES doubles per QP, independent of any reference solver.

@@ -33,6 +33,10 @@ struct RowGen {  // one addToProblem call of the builder, in the reference's ord
   int32_t rows;
 };
 
+// solver_flags bit (include/mgqp_amd.h MGQP_SOLVER_UNIT_HESSIAN): the level solves go through
+// qpgpu_solve_batched_unit; stripped before the solver's descriptor is filled
+constexpr uint32_t kSolverUnitHessian = 0x10000u;
+
 struct Plan {
   int32_t dof, ws, dim, ngen, nlevels, total_rows, nineq;
   int32_t level_rows[kMaxLevels], level_row0[kMaxLevels];
@@ -49,7 +53,8 @@ struct Plan {
   const float* h;        // [count][dof]
   const float* inertia;  // [count][dof][dof]
   int32_t status_len;
-  uint32_t solver_flags;  // QPGPU_FLAG_* of the level solves (host side only)
+  // QPGPU_FLAG_* of the level solves, and kSolverUnitHessian (host side only)
+  uint32_t solver_flags;
   // limits configuration (already size-normalised on the host, :1113-1117)
   float accP[kMaxDof], accN[kMaxDof], tP[kMaxDof], tN[kMaxDof], sup[kMaxDof], inf[kMaxDof];
 };
@@ -78,7 +83,7 @@ int launch_finish_level(const Plan& P, const Work& W, int level, const double* x
                         const int32_t* st2, int acc_rows, hipStream_t s);
 int launch_outputs(const Plan& P, const Work& W, float* torques, float* tracking, int32_t* codes,
                    hipStream_t s);
-int launch_init(const Plan& P, const Work& W, double* G, double* g0, hipStream_t s);
+int launch_init(const Plan& P, const Work& W, double* G, double* g0, bool init_g0, hipStream_t s);
 
 // The whole cycle: workspace (grow-only, cached per device), init, builder, every level with a
 // solve (solve with CI, solve without CI, finish), outputs.  Bcumul_host: nineq x dim floats.

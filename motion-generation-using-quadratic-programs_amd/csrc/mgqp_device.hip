@@ -88,7 +88,7 @@ __global__ void build_tasks_kernel(Plan P, Work W) {
   }
 }
 
-__global__ void init_kernel(Plan P, Work W, double* G, double* g0, int init_qp) {
+__global__ void init_kernel(Plan P, Work W, double* G, double* g0, int init_G, int init_g0) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t K = W.count;
   if (r >= K) return;
@@ -99,10 +99,10 @@ __global__ void init_kernel(Plan P, Work W, double* G, double* g0, int init_qp) 
     W.u[(int64_t)i * K + r] = 0.f;
   }
   W.state[r] = 0;
-  if (init_qp) {
+  if (init_G)
     for (int i = 0; i < dim * dim; ++i) G[r * dim * dim + i] = (i / dim == i % dim) ? 1.0 : 0.0;
+  if (init_g0)
     for (int i = 0; i < dim; ++i) g0[r * dim + i] = 0.0;
-  }
 }
 
 // ------------------------------------------------------------------ level QP (:783-793, :655-708)
@@ -461,9 +461,9 @@ dim3 grid_for(int64_t K, int bs) { return dim3((unsigned)((K + bs - 1) / bs)); }
 
 }  // namespace
 
-int launch_init(const Plan& P, const Work& W, double* G, double* g0, hipStream_t s) {
+int launch_init(const Plan& P, const Work& W, double* G, double* g0, bool init_g0, hipStream_t s) {
   hipLaunchKernelGGL(init_kernel, grid_for(W.count, 256), dim3(256), 0, s, P, W, G, g0,
-                     G != nullptr ? 1 : 0);
+                     G != nullptr ? 1 : 0, init_g0 ? 1 : 0);
   return check(hipGetLastError());
 }
 
@@ -566,6 +566,13 @@ int fail(const char* what, hipError_t e, const char** err) {
 int run_cycle(const Plan& P, int64_t K, const float* Bcumul_host, float* torques, float* tracking,
               int32_t* codes, hipStream_t s, const char** err) {
   if (K <= 0) return 0;
+  // the opt-in unit-Hessian solves (qpgpu_solve_batched_unit): no fast form exists
+  const bool unit = (P.solver_flags & kSolverUnitHessian) != 0;
+  if (unit && (P.solver_flags & QPGPU_FLAG_FAST)) {
+    g_cws_err = "MGQP_SOLVER_UNIT_HESSIAN cannot be combined with QPGPU_FLAG_FAST";
+    *err = g_cws_err.c_str();
+    return -1;
+  }
   const int n = P.dim, m = P.nineq;
   int pmax = 0;
   for (int l = 0; l < P.nlevels; ++l) pmax = P.level_rows[l] > pmax ? P.level_rows[l] : pmax;
@@ -633,11 +640,21 @@ int run_cycle(const Plan& P, int64_t K, const float* Bcumul_host, float* torques
   // The solver leaves G = I and g0 = 0 as they are, so they are written once per (count, dim) and
   // place: the arrays in front of them grow with the task stack's rows, so another stack of the
   // same count and dim has them elsewhere, over what the last cycle left there.
-  const bool init_qp = !(g_cws.qp_count == K && g_cws.qp_dim == n && g_cws.qp_off == oG);
-  if (launch_init(P, W, init_qp ? G : nullptr, g0, s)) return fail("init", hipGetLastError(), err);
-  g_cws.qp_count = K;
-  g_cws.qp_dim = n;
-  g_cws.qp_off = oG;
+  // A unit cycle neither writes nor reads the G region.  Where its layout is the recorded one
+  // (same count, dim and place) every array lies where the dense cycle's does and the record
+  // stays true; with any other layout its arrays (g0, CE, ce0, V, ...) land over the recorded G and
+  // g0, so the record is dropped and the next dense cycle writes them again.  It writes its own
+  // g0 = 0 every time (n doubles per robot) rather than keep a second record of where zeros lie.
+  const bool recorded = g_cws.qp_count == K && g_cws.qp_dim == n && g_cws.qp_off == oG;
+  const bool init_qp = !unit && !recorded;
+  if (launch_init(P, W, init_qp ? G : nullptr, g0, init_qp || unit, s)) return fail("init", hipGetLastError(), err);
+  if (!unit) {
+    g_cws.qp_count = K;
+    g_cws.qp_dim = n;
+    g_cws.qp_off = oG;
+  } else if (!recorded) {
+    g_cws.qp_count = -1;
+  }
   if (launch_build_tasks(P, W, s)) return fail("build_tasks", hipGetLastError(), err);
 
   int last = -1;
@@ -652,13 +669,14 @@ int run_cycle(const Plan& P, int64_t K, const float* Bcumul_host, float* torques
     d.p = p;
     d.m = m;
     d.batch = K;
-    d.flags = P.solver_flags;
+    d.flags = P.solver_flags & ~kSolverUnitHessian;
     // one launch gives both the solve with CI and the retry without it (:717-736): the latter
     // is the state after the equality phase (qpgpu_solve_batched_eq)
-    const int rc = qpgpu_solve_batched_eq(&d, G, g0, CE, ce0, CI, ci0, x1, f1, s1, nullptr, x2,
-                                          f2, s2, s);
+    const int rc = unit ? qpgpu_solve_batched_unit(&d, g0, CE, ce0, CI, ci0, x1, f1, s1, nullptr, x2, f2, s2, s)
+                        : qpgpu_solve_batched_eq(&d, G, g0, CE, ce0, CI, ci0, x1, f1, s1, nullptr, x2,
+                                                 f2, s2, s);
     if (rc != QPGPU_SUCCESS) {
-      g_cws_err = std::string("qpgpu_solve_batched_eq: ") + qpgpu_last_error();
+      g_cws_err = std::string(unit ? "qpgpu_solve_batched_unit: " : "qpgpu_solve_batched_eq: ") + qpgpu_last_error();
       *err = g_cws_err.c_str();
       return -3;
     }

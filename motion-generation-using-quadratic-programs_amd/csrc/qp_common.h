@@ -320,7 +320,7 @@ struct QpArgs {
   int tile;  // 1 = QP-major, 64 = TILED64
   int64_t batch;
   uint32_t flags;
-  double* G;
+  double* G;  // NULL in a launch of the unit-Hessian kernels (qpgpu_solve_batched_unit), which never read it
   const double* g0;
   const double* CE;
   const double* ce0;
@@ -479,6 +479,16 @@ const char* qpk_medium_name_fast(int n, int m, int mode);  // ... with QPGPU_WAV
 int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a);  // device workspace of a launch (0 = none)
 hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream, double* ws);
 hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream);
+// The unit-Hessian builds (qpgpu_solve_batched_unit: G = I stated, a->G never read; plain mode
+// only, so no mode argument): qp_lane_unit.hip / qp_lane_unit_u.hip, qp_small.hip's fifth kernel,
+// qp_wave_unit.hip (the LDS variants).  A name is NULL where the family's unit build lacks the shape.
+const char* qpk_lane_name_unit(int n, int m);
+hipError_t qpk_launch_lane_unit(const qpk::QpArgs* a, hipStream_t stream);
+hipError_t qpk_launch_lane_unit_u(const qpk::QpArgs* a, hipStream_t stream);  // kArgStage16 not set
+const char* qpk_small_name_unit(int n, int m);
+hipError_t qpk_launch_small_unit(const qpk::QpArgs* a, hipStream_t stream);
+const char* qpk_medium_name_unit(int n, int m);
+hipError_t qpk_launch_medium_unit(const qpk::QpArgs* a, hipStream_t stream);
 const char* qpk_generic_name(int n, int m, int mode);  // qp_generic.hip
 int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch);
 hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws);

@@ -47,7 +47,27 @@
 #ifndef QPGPU_LANE_UNALIGNED
 #define QPGPU_LANE_UNALIGNED 0
 #endif
-#if QPGPU_LANE_FAST && QPGPU_LANE_UNALIGNED
+// The same source built with QPGPU_LANE_UNIT=1 (qp_lane_unit.hip, qp_lane_unit_u.hip) is the
+// kernel of qpgpu_solve_batched_unit: the Hessian is the identity, so the setup is stated instead
+// of computed — J = I, c1 = c2 = the sum of n ones, x0 = -g0, f0 = 0.5 sum g0[i] x0[i] — and a.G is
+// never read.  Only the run-time-shape instantiations, which carry the m = 0
+// snapshot, are built, in namespaces of their own: the kernels of the other builds are the code
+// they were.
+#ifndef QPGPU_LANE_UNIT
+#define QPGPU_LANE_UNIT 0
+#endif
+#if QPGPU_LANE_UNIT && QPGPU_LANE_FAST
+#error "the unit-Hessian lane kernels restate the reference's operation order only"
+#endif
+#if QPGPU_LANE_UNIT && QPGPU_LANE_UNALIGNED
+#define QPK_LANE_NS qpk_unit_u
+#define QP_LANE_KERNEL qp_lane_unit_kernel
+#define QPK_LANE_C(name) name##_unit_u
+#elif QPGPU_LANE_UNIT
+#define QPK_LANE_NS qpk_unit
+#define QP_LANE_KERNEL qp_lane_unit_kernel
+#define QPK_LANE_C(name) name##_unit
+#elif QPGPU_LANE_FAST && QPGPU_LANE_UNALIGNED
 #define QPK_LANE_NS qpk_fast_u
 #define QP_LANE_KERNEL qp_lane_fast_kernel
 #define QPK_LANE_C(name) name##_fast_u
@@ -347,10 +367,14 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   bool chol_ok = live;  // idle lanes (past the batch) never touch LDS slots
   double bad_sum = 0.0;
   {
+#if !QPGPU_LANE_UNIT
     double Gr[NM][NM];
-    // round A: G and g0
+#endif
+    // round A: G and g0 (the unit build: g0 only)
     const int offg0 = RB;
+#if !QPGPU_LANE_UNIT
     stage_all(a.G, n * n, 0);
+#endif
     stage_all(a.g0, n, offg0);
     __syncthreads();
     // The LDS reads are unconditional (in range for every lane; an idle lane's slot holds stale
@@ -359,11 +383,13 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     double g0v[NM];
 #pragma unroll
     for (int i = 0; i < NM; i++) {
+#if !QPGPU_LANE_UNIT
 #pragma unroll
       for (int j = 0; j < NM; j++) {
         const double v = (i < n && j < n) ? rd_all(0, n * n, i * n + j) : 0.0;
         Gr[i][j] = live ? v : 0.0;
       }
+#endif
       const double v0 = i < n ? rd_all(offg0, n, i) : 0.0;
       g0v[i] = live ? v0 : 0.0;
     }
@@ -396,6 +422,18 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
           copy_chunk(c0, kQpw * p, offcB, (c - nce) * 128);
       }
     };
+#if QPGPU_LANE_UNIT
+    // G = I stated: c1 = c2 = the ascending sum of n ones, J = I, x0 = -g0 and f0 from it.  Nothing
+    // is factored, so round B has no Cholesky rows to go between.  Its NM parts still go one per
+    // trip of this loop, back to back: measured against one round_b(0, 1) ahead of the loop, which
+    // is the same copies in another instruction order, that form was 2 % slower on (7, 6, 14) and
+    // within the spread on (7, 0, 14).
+#pragma unroll
+    for (int i = 0; i < NM; i++) {
+      round_b(i, NM);
+      if (i < n) c1 += 1.0;
+    }
+#else
 #pragma unroll
     for (int i = 0; i < NM; i++)
       if (i < n) c1 += Gr[i][i];
@@ -435,6 +473,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         for (int j = 0; j < NM; j++)
           if (i < n && j < n) Gw[(i * n + j) * T] = Gr[i][j];
     }
+#endif  // !QPGPU_LANE_UNIT
     // round B lands: the staged CE / ce0 are read in the equality phase.  Called once, after
     // J = L^-T and the solve (which need only the factor), so the CE transfer lands under them
     // instead of stalling the wave after the Cholesky.  (A lambda still: with the body written
@@ -470,6 +509,23 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
       }
     }
     };
+#if QPGPU_LANE_UNIT
+    if (chol_ok) {
+#pragma unroll
+      for (int r = 0; r < NM; r++) {
+#pragma unroll
+        for (int j = 0; j < NM; j++) Jreg[r][j] = (r < n && j == r) ? 1.0 : 0.0;
+        if (r < n) c2 += 1.0;
+      }
+      // (entries past n are -0.0, as the dense setup's negation of the +0.0 it starts from)
+#pragma unroll
+      for (int i = 0; i < NM; i++) xv[i] = -g0v[i];
+#pragma unroll
+      for (int i = 0; i < NM; i++)
+        if (i < n) fval += g0v[i] * xv[i];
+      fval = 0.5 * fval;
+    }
+#else
     if (chol_ok) {
       // J = L^{-T}: row r of J = L^{-1} e_r (forward_elimination); c2 = trace(J).
       // With a finite L the first r entries of L^{-1} e_r are exactly +0.0 (0.0 - L*(+0) and
@@ -542,6 +598,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         if (i < n) fval += g0v[i] * xv[i];
       fval = 0.5 * fval;
     }
+#endif  // QPGPU_LANE_UNIT
     land_round_b();
   }
   lstamp(a, 1);
@@ -1533,6 +1590,35 @@ __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
   }
 }
 
+#if QPGPU_LANE_UNIT
+// The unit build's launch: the run-time-shape instantiation of each size class in both layouts
+// (EXACT = false, PX = -1: the ones that carry the m = 0 snapshot), nothing else.
+template <int NM, int MM>
+static hipError_t launch_lane_unit(const QpArgs& a, hipStream_t stream) {
+  const dim3 g((unsigned)((a.batch + kQpw - 1) / kQpw)), blk(64);
+  if (a.tile == 64)
+    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, 64, false, -1>), g, blk, 0, stream, a);
+  else
+    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, 1, false, -1>), g, blk, 0, stream, a);
+  return hipGetLastError();
+}
+}  // namespace QPK_LANE_NS
+
+extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream) {
+  if (a->u || a->hi) return hipErrorInvalidValue;  // no dual or box form
+  if (a->n <= 7 && a->m <= 14) return QPK_LANE_NS::launch_lane_unit<7, 14>(*a, stream);
+  if (a->n <= 8 && a->m <= 16) return QPK_LANE_NS::launch_lane_unit<8, 16>(*a, stream);
+  return hipErrorInvalidValue;
+}
+#if !QPGPU_LANE_UNALIGNED  // the unaligned build runs what its aligned twin names
+extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m) {
+  if (n <= 7 && m <= 14) return "qp_lane_unit<N=7,M=14>";
+  if (n <= 8 && m <= 16) return "qp_lane_unit<N=8,M=16>";
+  return nullptr;
+}
+#endif
+#else  // QPGPU_LANE_UNIT
+
 // The full-wave aligned kernels (lane_body's FULL) of the exact aligned build: the shapes behind
 // C1 / C4 (7, 6, 14) and C2 (7, 0, 14), in both layouts.  Kernels of their own, not a branch in the
 // kernels above (which stay the code they were; a branch in the kernel once pushed the N = 8
@@ -1761,3 +1847,4 @@ extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m, int mode) {
 }
 #endif
 #endif  // QPGPU_LANE_PART == 2
+#endif  // QPGPU_LANE_UNIT

@@ -72,6 +72,7 @@ struct SmallCfg {
 
 // the kernel, and a second time with the multipliers carried and returned (a kernel of its own,
 // so the first is the same code as without it)
+#define QP_SMALL_UNIT 0
 #define QP_SMALL_BOX false
 #define QP_SMALL_KERNEL qp_small_kernel
 #define QP_SMALL_DUAL false
@@ -98,6 +99,17 @@ struct SmallCfg {
 #undef QP_SMALL_KERNEL
 #undef QP_SMALL_DUAL
 #undef QP_SMALL_BOX
+#undef QP_SMALL_UNIT
+// a fifth time for the identity Hessian without a G array (qpgpu_solve_batched_unit)
+#define QP_SMALL_UNIT 1
+#define QP_SMALL_KERNEL qp_small_unit_kernel
+#define QP_SMALL_DUAL false
+#define QP_SMALL_BOX false
+#include "qp_small_kernel.inc"
+#undef QP_SMALL_KERNEL
+#undef QP_SMALL_DUAL
+#undef QP_SMALL_BOX
+#undef QP_SMALL_UNIT
 
 // ------------------------------------------------------------------------------------------
 // launch table
@@ -137,6 +149,31 @@ static const SmallVariant kSmallVariants[] = {
     {16, 64, QPK_SMALL_NAMES("S=16,N=16,M=64"), launch_small<16, 16, 64>},
 };
 
+// the unit-Hessian kernel of each variant (no dual or box form)
+template <int S, int NM, int MM>
+static hipError_t launch_small_unit(const QpArgs& a, hipStream_t stream) {
+  using C = SmallCfg<S, NM, MM>;
+  const dim3 g((unsigned)((a.batch + C::QPW - 1) / C::QPW)), blk(64);
+  hipLaunchKernelGGL((qp_small_unit_kernel<S, NM, MM>), g, blk, 0, stream, a);
+  return hipGetLastError();
+}
+struct SmallUnitVariant {
+  int nmax, mmax;
+  const char* name;
+  hipError_t (*launch)(const QpArgs&, hipStream_t);
+};
+static const SmallUnitVariant kSmallUnitVariants[] = {
+    {8, 16, "qp_small_unit<S=8,N=8,M=16>", launch_small_unit<8, 8, 16>},
+    {8, 32, "qp_small_unit<S=8,N=8,M=32>", launch_small_unit<8, 8, 32>},
+    {16, 32, "qp_small_unit<S=16,N=16,M=32>", launch_small_unit<16, 16, 32>},
+    {16, 64, "qp_small_unit<S=16,N=16,M=64>", launch_small_unit<16, 16, 64>},
+};
+const SmallUnitVariant* pick_small_unit(int n, int m) {
+  for (const auto& v : kSmallUnitVariants)
+    if (n <= v.nmax && m <= v.mmax) return &v;
+  return nullptr;
+}
+
 const SmallVariant* pick_small(int n, int m) {
   for (const auto& v : kSmallVariants)
     if (n <= v.nmax && m <= v.mmax) return &v;  // any p: iq never exceeds n
@@ -153,4 +190,14 @@ extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream)
 extern "C" const char* qpk_small_name(int n, int m, int mode) {
   const qpk::SmallVariant* v = qpk::pick_small(n, m);
   return v ? v->name[mode] : nullptr;
+}
+
+extern "C" hipError_t qpk_launch_small_unit(const qpk::QpArgs* a, hipStream_t stream) {
+  const qpk::SmallUnitVariant* v = qpk::pick_small_unit(a->n, a->m);
+  return (v && !a->u && !a->hi) ? v->launch(*a, stream) : hipErrorInvalidValue;
+}
+
+extern "C" const char* qpk_small_name_unit(int n, int m) {
+  const qpk::SmallUnitVariant* v = qpk::pick_small_unit(n, m);
+  return v ? v->name : nullptr;
 }

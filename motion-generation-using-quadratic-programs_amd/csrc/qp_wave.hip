@@ -36,7 +36,21 @@
 #ifndef QPGPU_WAVE_FAST
 #define QPGPU_WAVE_FAST 0
 #endif
-#if QPGPU_WAVE_FAST
+// The same source built with QPGPU_WAVE_UNIT=1 (qp_wave_unit.hip) is the kernel of
+// qpgpu_solve_batched_unit for the LDS variants: the Hessian is the identity, so the setup is
+// stated instead of computed — J = I, c1 = c2 = the sum of n ones, x0 = -g0, f0 from it — and a.G
+// is never read.  A build of its own: the kernels of the other two are the code
+// they were.
+#ifndef QPGPU_WAVE_UNIT
+#define QPGPU_WAVE_UNIT 0
+#endif
+#if QPGPU_WAVE_UNIT && QPGPU_WAVE_FAST
+#error "the unit-Hessian wave kernels restate the reference's operation order only"
+#endif
+#if QPGPU_WAVE_UNIT
+#define QPK_WAVE_NS qpk_wunit
+#define QP_WAVE_KERNEL qp_wave_unit_kernel
+#elif QPGPU_WAVE_FAST
 #define QPK_WAVE_NS qpk_wfast
 #define QP_WAVE_KERNEL qp_wave_fast_kernel
 #else
@@ -486,7 +500,9 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
   const int n = a.n, p = a.p, m = a.m, T = a.tile;
   const double inf = dinf();
   const int64_t bb = live ? b : 0;
+#if !QPGPU_WAVE_UNIT
   const double* Gb = a.G + qbase_rt(bb, n * n, T);
+#endif
   const double* g0b = a.g0 + qbase_rt(bb, n, T);
   const double* CEb = a.CE + qbase_rt(bb, n * p, T);
   const double* ce0b = a.ce0 + qbase_rt(bb, p, T);
@@ -555,6 +571,48 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
     if (live)
       for (int i = ls; i < n; i += S) note_x(xv[i]);  // (ctl->xh was cleared before the sync)
   }
+#if QPGPU_WAVE_UNIT
+  // G = I stated (qpgpu_solve_batched_unit): nothing is loaded from G and nothing is factored.
+  // Each lane writes its part of J = I (+0.0 off the diagonal) and of x0 = -g0, g0 itself into the
+  // z region as the dense setup leaves it; the lead writes c1 = c2 = the ascending sum of n ones
+  // and f0 = 0.5 sum g0[i] x0[i], each product rounded, ascending from +0.0.
+  static_assert(!GJR && !F && !DUAL && !BOX, "the unit build has the plain LDS variants only");
+  (void)Lm;
+  if (lead) {
+    ctl->unc = 0;
+    ctl->status = QPGPU_QP_OK;
+    ctl->iter = 0;
+    ctl->steps = 0;
+    ctl->phase = live ? PH_SCAN : PH_DONE;
+    ctl->fin = 1;
+  }
+  if (live) {
+    for (int e = ls; e < n * JS; e += S) {
+      const int i = e / JS;
+      Jm[e] = (e - i * JS == i) ? 1.0 : 0.0;
+    }
+    for (int i = ls; i < n; i += S) {
+      const double g = EL(g0b, i);
+      zv[i] = g;
+      xv[i] = -g;
+    }
+  }
+  grp_sync<S>();
+  qp_stamp(a, 1);
+  const bool chol_ok = live;
+  if (lead && live) {
+    double c = 0.0;
+    for (int i = 0; i < n; i++) c += 1.0;
+    ctl->c1 = c;
+    ctl->c2 = c;
+    double f = 0.0;
+    for (int i = 0; i < n; i++) f += zv[i] * xv[i];
+    ctl->f = 0.5 * f;
+    ctl->R_norm = 1.0;
+    ctl->iq = 0;
+  }
+  grp_sync<S>();
+#else
   // G -> R region (becomes L), g0 -> z region
   if (live && !pre) {
     if constexpr (NMAX <= S && NMAX <= 64) {
@@ -808,6 +866,7 @@ __device__ __forceinline__ bool wave_body(const QpArgs& a, double* __restrict__ 
       grp_sync<S>();
     }
   }
+#endif  // QPGPU_WAVE_UNIT
   if (chol_ok) {
     // R = 0 (L no longer needed), flags
     for (int e = ls; e < (kPackedR ? Ly.nr : n * JS); e += S) Rm[e] = 0.0;
@@ -2491,7 +2550,7 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : OCC)
   }
 }
 
-#if !QPGPU_WAVE_FAST
+#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
 // qpgpu_solve_batched_dual: a kernel of its own (one per variant, the OCC = 1 layout), so the
 // kernels above are the same code as without it
 template <int S, int NMAX, int MMAX, bool GJR>
@@ -2536,7 +2595,7 @@ static hipError_t grant_dynamic_lds(WaveKernel kernel, size_t bytes) {
   return hipSuccess;
 }
 
-#if !QPGPU_WAVE_FAST
+#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
 // the dual, box and box-dual kernels: the OCC = 1 instantiation's layout, R packed where that one
 // sets up in registers
 template <int S, int NMAX, int MMAX, bool GJR>
@@ -2560,7 +2619,7 @@ static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
   const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
   // the three other modes run kernels that only the exact build has: in the fast build an error
   switch (mode_of(a)) {
-#if !QPGPU_WAVE_FAST
+#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
     case kBoxDual:
       return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
     case kBox:
@@ -2614,7 +2673,9 @@ struct WaveVariant {
   hipError_t (*launch)(const QpArgs&, hipStream_t, double*);
 };
 
-#if QPGPU_WAVE_FAST
+#if QPGPU_WAVE_UNIT
+#define QPK_WAVE_NAMES(plain, s) {"qp_wave_unit<" s ">", nullptr, nullptr, nullptr}
+#elif QPGPU_WAVE_FAST
 #define QPK_WAVE_NAMES(plain, s) {"qp_wave_fast<" s ">", nullptr, nullptr, nullptr}
 #else
 #define QPK_WAVE_NAMES(plain, s) {plain "qp_wave<" s ">", "qp_wave_dual<" s ">", "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"}
@@ -2626,7 +2687,7 @@ static const WaveVariant kWaveVariants[] = {
     {32, 128, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=128"), launch_wave<32, 32, 128, false>},
     {64, 128, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=128"), launch_wave<64, 64, 128, false>},
     {64, 256, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=256"), launch_wave<64, 64, 256, false>},
-#if !QPGPU_WAVE_FAST
+#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
     // (the plain mode's default is the panel path; the other modes always run EXACT, without it)
     {256, 1024, WaveCfg<256, 256, 1024, true>::WS_DOUBLES,
      QPK_WAVE_NAMES("qp_panel<MFMA f64 16x16x4> + ", "S=256,N=256,M=1024,global J/R"),
@@ -2642,7 +2703,17 @@ const WaveVariant* pick_wave(int n, int m) {
 
 }  // namespace QPK_WAVE_NS
 
-#if QPGPU_WAVE_FAST
+#if QPGPU_WAVE_UNIT
+// the unit build covers the LDS variants only (n <= 64, m <= 256), in the plain mode
+extern "C" const char* qpk_medium_name_unit(int n, int m) {
+  const qpk_wunit::WaveVariant* v = qpk_wunit::pick_wave(n, m);
+  return v ? v->name[0] : nullptr;
+}
+extern "C" hipError_t qpk_launch_medium_unit(const qpk::QpArgs* a, hipStream_t stream) {
+  const qpk_wunit::WaveVariant* v = qpk_wunit::pick_wave(a->n, a->m);
+  return v ? v->launch(*a, stream, nullptr) : hipErrorInvalidValue;
+}
+#elif QPGPU_WAVE_FAST
 // the fast build covers the LDS variants only (n <= 64, m <= 256); wider shapes keep the
 // default path (its n > 64 form is already the 1e-10 tolerance mode)
 extern "C" const char* qpk_medium_name_fast(int n, int m, int mode) {

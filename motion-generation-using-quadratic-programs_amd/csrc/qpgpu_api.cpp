@@ -187,6 +187,28 @@ static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode) {
   return {};
 }
 
+// The selection of qpgpu_solve_batched_unit: the same family order over the families'
+// unit builds — lane, subgroup (only where default_small), the wave kernel's LDS variants — and
+// nothing beyond them: n > 64, m > 256 and QPGPU_FLAG_FORCE_GENERIC have no kernel, and neither do
+// QPGPU_FLAG_FAST (there is no fast unit form) and QPGPU_FLAG_WRITE_FACTOR (there is no G).  A
+// selection of its own, so that select_kernel answers for the existing modes what it always has.
+static Pick select_kernel_unit(int n, int p, int m, uint32_t flags) {
+  if (!flags_valid(flags) || n <= 0 || p < 0 || m < 0) return {};
+  if (flags & (QPGPU_FLAG_FAST | QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_FORCE_GENERIC)) return {};
+  const uint32_t force = flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP | QPGPU_FLAG_FORCE_WAVE);
+  const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
+  const char* s;
+  if (may(QPGPU_FLAG_FORCE_LANE) && (s = qpk_lane_name_unit(n, m))) return {kLane, false, s};
+  if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name_unit(n, m)))
+    return {kSmall, false, s};
+  if (may(QPGPU_FLAG_FORCE_WAVE) && (s = qpk_medium_name_unit(n, m))) return {kWave, false, s};
+  return {};
+}
+
+const char* qpgpu_kernel_name_unit(int32_t n, int32_t p, int32_t m, uint32_t flags) {
+  return select_kernel_unit(n, p, m, flags).name;
+}
+
 const char* qpgpu_kernel_name_flags(int32_t n, int32_t p, int32_t m, uint32_t flags) {
   return select_kernel(n, p, m, flags, qpk::kPlain).name;
 }
@@ -284,13 +306,15 @@ static int launch_generic(const qpk::QpArgs& a, hipStream_t s, std::unique_lock<
 }
 
 // What every device-pointer entry ends in, after validate(d) and its own rules: the empty batch,
-// the NULL checks of the common arrays, the selection, the launch.
-static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream) {
+// the NULL checks of the common arrays, the selection, the launch.  unit: the entry without a G
+// array (qpgpu_solve_batched_unit) — a.G is NULL and the families' unit builds run.
+static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream, bool unit = false) {
   if (d->batch == 0) return QPGPU_SUCCESS;
-  if (!a.G || !a.g0 || !a.x || !a.f || !a.status) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((!unit && !a.G) || !a.g0 || !a.x || !a.f || !a.status) return QPGPU_ERR_INVALID_ARGUMENT;
   if ((a.p > 0 && (!a.CE || !a.ce0)) || (!a.hi && a.m > 0 && (!a.CI || !a.ci0)))
     return QPGPU_ERR_INVALID_ARGUMENT;
-  const Pick k = select_kernel(a.n, a.p, a.m, d->flags, qpk::mode_of(a));
+  const Pick k = unit ? select_kernel_unit(a.n, a.p, a.m, d->flags)
+                      : select_kernel(a.n, a.p, a.m, d->flags, qpk::mode_of(a));
   if (k.family == kNone) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
   // no elements has a NULL data_ptr; the box kernels never read CI / ci0.  The wave kernels' l1
@@ -304,6 +328,25 @@ static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   std::unique_lock<std::mutex> ws_hold;  // the workspace cache's lock, until the launches are enqueued
   hipError_t e = hipSuccess;
+  if (unit) {
+    // (the lane kernels' staged group is g0, CE and ce0 here: alignment_flags saw a NULL G)
+    switch (k.family) {
+      case kLane:
+        e = (a.flags & qpk::kArgStage16) ? qpk_launch_lane_unit(&a, s) : qpk_launch_lane_unit_u(&a, s);
+        break;
+      case kSmall:
+        e = qpk_launch_small_unit(&a, s);
+        break;
+      case kWave:
+        e = qpk_launch_medium_unit(&a, s);
+        break;
+      default:
+        e = hipErrorInvalidValue;
+        break;
+    }
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return QPGPU_SUCCESS;
+  }
   switch (k.family) {
     case kLane:
       // The lane kernels stage G, g0, CE and ce0 by 16-byte LDS-DMA: launched only when those arrays
@@ -357,6 +400,28 @@ int qpgpu_solve_batched_eq(const qpgpu_problem_desc* d, double* G, const double*
   a.f_eq = f_eq;
   a.st_eq = status_eq;
   return run(d, a, stream);
+}
+
+// The identity Hessian without a G array (include/qpgpu.h).  The unit kernels restate
+// the reference's operation order only, so the call runs as if QPGPU_FLAG_EXACT were set;
+// QPGPU_FLAG_FAST and QPGPU_FLAG_WRITE_FACTOR are refused.  The m = 0 snapshot is all three arrays
+// or none.  Every rule is decided from the descriptor and the pointers' values before anything is
+// launched; no workspace, one kernel, so the first call for a shape can be captured.
+int qpgpu_solve_batched_unit(const qpgpu_problem_desc* d, const double* g0, const double* CE,
+                             const double* ce0, const double* CI, const double* ci0, double* x,
+                             double* f, int32_t* status, int32_t* iters, double* x_eq, double* f_eq,
+                             int32_t* status_eq, void* stream) {
+  const int rc = validate(d);
+  if (rc) return rc;
+  if (d->flags & (QPGPU_FLAG_FAST | QPGPU_FLAG_WRITE_FACTOR)) return QPGPU_ERR_INVALID_ARGUMENT;
+  const int eq = (x_eq ? 1 : 0) + (f_eq ? 1 : 0) + (status_eq ? 1 : 0);
+  if (eq != 0 && eq != 3) return QPGPU_ERR_INVALID_ARGUMENT;
+  qpk::QpArgs a = make_args(d, nullptr, g0, CE, ce0, CI, ci0, x, f, status, iters);
+  a.flags |= QPGPU_FLAG_EXACT;
+  a.x_eq = x_eq;
+  a.f_eq = f_eq;
+  a.st_eq = status_eq;
+  return run(d, a, stream, true);
 }
 
 // The multipliers too (include/qpgpu.h).  The dual kernels restate the reference's operation

@@ -270,13 +270,18 @@ class Controller:
         return codes, tq, tr
 
 
-def _update_device(self, dsc: "DeviceScenario", out=None, stream=None, fast: bool = False):
+SOLVER_UNIT_HESSIAN = 0x10000  # MGQP_SOLVER_UNIT_HESSIAN (include/mgqp_amd.h)
+
+
+def _update_device(self, dsc: "DeviceScenario", out=None, stream=None, fast: bool = False, unit: bool = False):
     """The device-resident cycle (mgqp_update_device).  Returns (rc, codes, torques, tracking)
     as torch tensors on the scenario's device (enqueued on `stream`, not synchronised).
-    fast=True solves the levels with the wave kernel's QPGPU_FLAG_FAST build (1e-10)."""
+    fast=True solves the levels with the wave kernel's QPGPU_FLAG_FAST build (1e-10).
+    unit=True solves them with qpgpu_solve_batched_unit (MGQP_SOLVER_UNIT_HESSIAN): the same
+    outputs bit for bit, without the identity matrices; not together with fast (raises)."""
     import torch
 
-    dsc.c.solver_flags = 0x4 if fast else 0  # QPGPU_FLAG_FAST
+    dsc.c.solver_flags = (0x4 if fast else 0) | (SOLVER_UNIT_HESSIAN if unit else 0)  # QPGPU_FLAG_FAST
 
     dev = next(iter(dsc.tensors.values())).device
     if out is None:

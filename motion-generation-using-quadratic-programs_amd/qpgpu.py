@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "qpgpu_kernel_name_box",
     "qpgpu_solve_batched_box_dual",
     "qpgpu_kernel_name_box_dual",
+    "qpgpu_solve_batched_unit",
+    "qpgpu_kernel_name_unit",
     "qpgpu_kkt_residuals",
     "qpgpu_kkt_residuals_box",
     "qpgpu_vjp",
@@ -128,6 +130,10 @@ def _load():
     lib.qpgpu_solve_batched_box_dual.restype = ctypes.c_int
     lib.qpgpu_kernel_name_box_dual.argtypes = [ctypes.c_int32] * 2 + [ctypes.c_uint32]
     lib.qpgpu_kernel_name_box_dual.restype = ctypes.c_char_p
+    lib.qpgpu_solve_batched_unit.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 13
+    lib.qpgpu_solve_batched_unit.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_unit.argtypes = [ctypes.c_int32] * 3 + [ctypes.c_uint32]
+    lib.qpgpu_kernel_name_unit.restype = ctypes.c_char_p
     lib.qpgpu_kkt_residuals.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
     lib.qpgpu_kkt_residuals.restype = ctypes.c_int
     lib.qpgpu_kkt_residuals_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 11
@@ -211,6 +217,13 @@ def kernel_name_box_dual(n: int, p: int, flags: int = 0) -> str:
     """The kernel a qpgpu_solve_batched_box_dual launch of shape (n, p) with `flags` runs ("" where
     kernel_name_box is ""); every such name contains "box" and "dual"."""
     return LIB.qpgpu_kernel_name_box_dual(n, p, flags).decode()
+
+
+def kernel_name_unit(n: int, p: int, m: int, flags: int = 0) -> str:
+    """The kernel a qpgpu_solve_batched_unit launch of shape (n, p, m) with `flags` runs; every
+    such name contains "unit".  "" where the entry refuses: n > 64, m > 256, FLAG_FORCE_GENERIC,
+    FLAG_FAST, FLAG_WRITE_FACTOR, a forced family that lacks the shape."""
+    return LIB.qpgpu_kernel_name_unit(n, p, m, flags).decode()
 
 
 def kernel_name_vjp(n: int, p: int = 0, m: int = 0) -> str:
@@ -379,6 +392,38 @@ class BoxProblems:
                         self.ce0.copy(), np.ascontiguousarray(CI), np.ascontiguousarray(ci0))
 
 
+@dataclass
+class UnitProblems:
+    """A batch of QPs whose Hessian is the identity, min 1/2 x^T x + g0^T x under the constraints
+    (qpgpu_solve_batched_unit): no G array.  numpy float64, QP-major."""
+
+    n: int
+    p: int
+    m: int
+    g0: np.ndarray  # (B, n)
+    CE: np.ndarray  # (B, n, p)
+    ce0: np.ndarray  # (B, p)
+    CI: np.ndarray  # (B, n, m)
+    ci0: np.ndarray  # (B, m)
+
+    @property
+    def batch(self) -> int:
+        return int(self.g0.shape[0])
+
+    def slice(self, b0: int, b1: int) -> "UnitProblems":
+        return UnitProblems(self.n, self.p, self.m, self.g0[b0:b1].copy(), self.CE[b0:b1].copy(),
+                            self.ce0[b0:b1].copy(), self.CI[b0:b1].copy(), self.ci0[b0:b1].copy())
+
+    def arrays(self):
+        return (self.g0, self.CE, self.ce0, self.CI, self.ci0)
+
+    def to_dense(self) -> Problems:
+        """The dense problem the unit entry is defined as: the same arrays and G = I."""
+        G = np.broadcast_to(np.eye(self.n), (self.batch, self.n, self.n)).copy()
+        return Problems(self.n, self.p, self.m, np.ascontiguousarray(G), self.g0.copy(), self.CE.copy(),
+                        self.ce0.copy(), self.CI.copy(), self.ci0.copy())
+
+
 def to_tiled64(a: np.ndarray) -> np.ndarray:
     """(B, ...) per-QP blocks -> TILED64 flat array of ceil(B/64) tiles (include/qpgpu.h)."""
     B = a.shape[0]
@@ -448,6 +493,11 @@ def algorithmic_bytes_per_qp(n: int, p: int, m: int) -> int:
 def algorithmic_bytes_per_qp_box(n: int, p: int) -> int:
     """The same count for the box entry: read G, g0, CE, ce0, hi, lo; write x and f."""
     return 8 * (n * n + n + n * p + p + 2 * n + n + 1)
+
+
+def algorithmic_bytes_per_qp_unit(n: int, p: int, m: int) -> int:
+    """The same count for the unit entry: read g0, CE, ce0, CI, ci0 (no G); write x and f."""
+    return 8 * (n + n * p + p + n * m + m) + 8 * (n + 1)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -730,6 +780,74 @@ class DeviceBoxBatch(_DeviceBatchBase):
         return self._launcher(stream, max_iter, FAMILY_FLAGS[family])
 
 
+class DeviceUnitBatch(_DeviceBatchBase):
+    """DeviceBatch for QPs with the identity as Hessian (qpgpu_solve_batched_unit): no G tensor."""
+
+    _INPUTS = ("g0", "CE", "ce0", "CI", "ci0")
+    _ENTRY = "qpgpu_solve_batched_unit"
+
+    def __init__(self, up: UnitProblems, device, with_iters: bool = True, layout=None):
+        super().__init__(up, device, with_iters, layout)
+        self.x_eq = self.f_eq = self.status_eq = None
+
+    def _eq_tensors(self):
+        import torch
+
+        if self.x_eq is None:
+            self.x_eq = torch.zeros_like(self.x)
+            self.f_eq = torch.zeros_like(self.f)
+            self.status_eq = torch.zeros_like(self.status)
+        return (self.x_eq, self.f_eq, self.status_eq)
+
+    def solve(self, stream=None, max_iter: int = 0, family=None, eq: bool = False, flags: int = 0):
+        """Enqueue one batched unit solve on `stream` (a torch.cuda.Stream, default current).
+        eq=True also writes the m = 0 answers into self.x_eq, self.f_eq, self.status_eq (allocated
+        at first use; eq_results() reads them).  `flags` are OR-ed in as given (tests pass
+        QPGPU_FLAG_FAST to see it refused)."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(self.x.device)
+        extra = self._eq_tensors() if eq else (None, None, None)
+        _, args = self._args(stream, max_iter, FAMILY_FLAGS[family] | flags, extra)
+        _check(LIB.qpgpu_solve_batched_unit(*args), self._ENTRY)
+
+    def launcher(self, stream, max_iter: int = 0, family=None, eq: bool = False):
+        """A zero-argument callable that enqueues this batch's solve on `stream` with every ctypes
+        argument prebuilt (see DeviceBatch.launcher)."""
+        extra = self._eq_tensors() if eq else (None, None, None)
+        d, args = self._args(stream, max_iter, FAMILY_FLAGS[family], extra)
+        fn, entry = LIB.qpgpu_solve_batched_unit, self._ENTRY
+
+        def launch():
+            rc = fn(*args)
+            if rc != SUCCESS:
+                _check(rc, entry)
+
+        launch._keep = (d, self)
+        return launch
+
+    def eq_results(self):
+        """(x_eq, f_eq, status_eq) of the last solve(eq=True) as numpy, x_eq (B, n) whatever the layout."""
+        x = self.x_eq.cpu().numpy()
+        if self.layout == LAYOUT_TILED64:
+            x = from_tiled64(x.reshape(-1), self.batch, (self.n,))
+        return x, self.f_eq.cpu().numpy(), self.status_eq.cpu().numpy()
+
+
+def solve_batched_unit(up: UnitProblems, family=None, layout=None, max_iter: int = 0, eq: bool = False,
+                       device="cuda:0"):
+    """Solve every QP of `up` on the GPU through qpgpu_solve_batched_unit: (x, f, status, iters) as
+    numpy, x of shape (B, n) whatever the device layout; with eq=True followed by (x_eq, f_eq,
+    status_eq), the answers of the same QPs without their inequalities."""
+    import torch
+
+    db = DeviceUnitBatch(up, device, layout=layout)
+    db.solve(max_iter=max_iter, family=family, eq=eq)
+    torch.cuda.synchronize(db.x.device)
+    return db.results() + (db.eq_results() if eq else ())
+
+
 def _solve_with_multipliers(db, pr, family, max_iter, write_factor):
     """The staging and unpacking solve_batched_dual and solve_batched_box_dual share: u and nact
     tensors for `db` (the device batch of `pr`), the solve, and every result as numpy in QP-major
@@ -993,6 +1111,16 @@ def make_box_problems(n: int, p: int, b0: int, b1: int, seed: int = 2026) -> Box
     pr = make_problems("box", n, p, 2 * n, b0, b1, seed)
     B = b1 - b0
     return BoxProblems(n, p, pr.G, pr.g0, pr.CE, pr.ce0, np.ones((B, n)), -np.ones((B, n)))
+
+
+def make_unit_problems(n: int, p: int, m: int, b0: int, b1: int, seed: int = 2026,
+                       g0_scale: float = 10.0) -> UnitProblems:
+    """QPs [b0, b1) of make_problems("general", n, p, m, ...) with G dropped (the identity stands
+    for it) and g0 ~ g0_scale N(0,1) (0.0 gives the controller's g0 = +0.0): the same CE, ce0, CI,
+    ci0, so the feasible point is the generator's."""
+    pr = make_problems("general", n, p, m, b0, b1, seed)
+    g0 = pr.g0 * (g0_scale / 10.0) if g0_scale != 0.0 else np.zeros_like(pr.g0)
+    return UnitProblems(n, p, m, np.ascontiguousarray(g0), pr.CE, pr.ce0, pr.CI, pr.ci0)
 
 
 def _make_range(kind: str, n: int, p: int, m: int, b0: int, b1: int, seed: int) -> Problems:

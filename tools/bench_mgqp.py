@@ -45,6 +45,9 @@ def main():
                          "active-set loop instead of the retry snapshot")
     ap.add_argument("--fast", action="store_true",
                     help="level solves with the wave kernel's QPGPU_FLAG_FAST build (within 1e-10)")
+    ap.add_argument("--unit", action="store_true",
+                    help="level solves through qpgpu_solve_batched_unit (MGQP_SOLVER_UNIT_HESSIAN: the same "
+                         "bits, no identity matrices read)")
     args = ap.parse_args()
 
     def configure(ctl):
@@ -61,21 +64,21 @@ def main():
     outs = []
     for j in range(S):  # one output set per stream (workspaces are per stream in the library)
         with torch.cuda.stream(streams[j]):
-            rc, codes, tq, tr = c.update_device(dsc, stream=streams[j].cuda_stream, fast=args.fast)
+            rc, codes, tq, tr = c.update_device(dsc, stream=streams[j].cuda_stream, fast=args.fast, unit=args.unit)
         outs.append((tq, tr, codes))
     for k in range(args.warmup):
-        c.update_device(dsc, out=outs[k % S], stream=streams[k % S].cuda_stream, fast=args.fast)
+        c.update_device(dsc, out=outs[k % S], stream=streams[k % S].cuda_stream, fast=args.fast, unit=args.unit)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        c.update_device(dsc, out=outs[k % S], stream=streams[k % S].cuda_stream, fast=args.fast)
+        c.update_device(dsc, out=outs[k % S], stream=streams[k % S].cuda_stream, fast=args.fast, unit=args.unit)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
     # serialized cycle time (one stream, HIP events)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(streams[0])
     for _ in range(3):
-        c.update_device(dsc, out=outs[0], stream=streams[0].cuda_stream, fast=args.fast)
+        c.update_device(dsc, out=outs[0], stream=streams[0].cuda_stream, fast=args.fast, unit=args.unit)
     e1.record(streams[0])
     torch.cuda.synchronize()
     ms_serial = e0.elapsed_time(e1) / 3
@@ -87,7 +90,8 @@ def main():
            "streams_outputs_identical": bool(same), "steps": args.steps, "warmup": args.warmup,
            "written_frac": ok, "dtype": "f32 glue + f64 QPs", "data": "synthetic",
            "limits": "wide (+-20 rad, gains 10/2)" if args.wide else "ops/mgqp.ops",
-           "level_solves": "fast (QPGPU_FLAG_FAST, 1e-10)" if args.fast else "exact (bitwise)"}
+           "level_solves": "fast (QPGPU_FLAG_FAST, 1e-10)" if args.fast else "exact (bitwise)",
+           "unit_hessian": bool(args.unit)}
 
     if not args.no_host:
         hs = mgqp.make_scenario(args.host_robots, seed=2026)
