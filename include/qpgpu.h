@@ -426,7 +426,7 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d,
  * dG is the gradient with respect to a SYMMETRIC G, the G the solver assumes (only its lower
  * triangle is read).  A constraint whose multiplier is exactly 0 is treated as inactive: x* is not
  * differentiable where a constraint is weakly active, and this is the one-sided choice made there.
- * Gradients of f or of the multipliers are not provided.
+ * Cotangents on f or on the multipliers are not taken here: qpgpu_vjp_full below takes them.
  *
  * Device pointers, enqueue only.  No workspace for any supported shape: the first call for a shape
  * can be captured into a hipGraph.  G, CE, CI, x, u and status are laid out exactly as
@@ -550,6 +550,57 @@ int qpgpu_vjp_box_ws(const qpgpu_problem_desc* d,
  * qpgpu_kernel_name_vjp's for n <= 64, a name containing "ws" for 64 < n <= 256, "" for n > 256 or
  * n <= 0. */
 const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t p, int32_t m);
+
+/* ---- the full backward step: cotangents on the multipliers and the optimal value too ---------------
+ * qpgpu_vjp_full and qpgpu_vjp_box_full are qpgpu_vjp_ws and qpgpu_vjp_box_ws with two more inputs.
+ * For a loss l(x, u, f) of everything a dual solve returns there are three cotangents per QP:
+ *     gx = dl/dx   n doubles in the layout of x          (required, as before: zeros if l ignores x)
+ *     gu = dl/du   p + m doubles in the layout of u      (box: p + 2n, the layout of
+ *                                                         qpgpu_solve_batched_box_dual); may be NULL
+ *     gf = dl/df   one double per QP, QP b's at gf[b] in EITHER layout, like f; may be NULL
+ * Everything said at qpgpu_vjp_ws holds unless stated here: shapes (n <= 256; n <= 64 does not
+ * touch the workspace, which may be NULL with workspace_bytes 0; 64 < n <= 256 takes
+ * qpgpu_vjp_workspace_bytes as it is, same slot size, same slot rule, results independent of the
+ * number of slots; n > 256 is QPGPU_ERR_UNSUPPORTED_SHAPE), the argument rules and their order, all
+ * decided before the device is touched, both layouts, natural alignment, sub-ranges, NULL outputs,
+ * status masking to +0.0, q > n giving NaN, enqueue only, no allocation, capturable first call.
+ *
+ * The mathematics.  With gl(t) the gu entry of the constraint at position t of W, the adjoint
+ * system is  G a + A c = gx,  A^T a = -gl:  a cotangent on the multipliers changes only the
+ * right-hand side of the q x q solve.  u of an inequality outside W is locally the constant 0 (the
+ * one-sided choice of qpgpu_vjp), so its gu entry never enters the arithmetic: it may hold
+ * anything, NaN included, without changing a bit of any output.  A cotangent on f needs no solve:
+ * by the envelope theorem df/dg0 = x, df/dG = 1/2 x x^T, df/dA = -x lam^T, df/db = -lam.
+ *
+ * The definition is qpgpu_vjp's with exactly two additions (tests/vjp_full_ref.py restates it).
+ *   With gu given:   r[t] = (sum_i M[i][t]*w[i]) + gl(t): the sum as before, gl(t) added once, after
+ *     it;  gl(t) = gu[t] for t < p,  gl(t) = gu[p+j] for inequality (or bound) j at position t.
+ *   With gf given, g = gf[b]:
+ *     hh = 0.5*g;  ah[i] = a[i] - hh*x[i];  dG[i][j] = -0.5 * (ah[i]*x[j] + x[i]*ah[j])  (bit-symmetric)
+ *     dg0[i] = -(a[i] - g*x[i])
+ *     ct[t] = c[t] + g*lam(t), and ct replaces c in dCE, dce0, dCI, dci0, dhi and dlo:
+ *     dCE[i][k] = a[i]*u[k] - x[i]*ct[k],  dce0[k] = -ct[k],  dhi[k] = -ct[t],  dlo[k] = +ct[t], ...
+ *     (a, not ah, stays in dCE and dCI;  y = w - M c still uses c).
+ * With gu == NULL and gf == NULL every output is bit-identical to qpgpu_vjp_ws / qpgpu_vjp_box_ws
+ * (and so to qpgpu_vjp for n <= 64): a NULL cotangent adds no operation, not even a + 0.0. */
+int qpgpu_vjp_full(const qpgpu_problem_desc* d,
+                   const double* G, const double* CE, const double* CI,
+                   const double* x, const double* u, const int32_t* status,
+                   const double* gx, const double* gu, const double* gf,
+                   double* dG, double* dg0, double* dCE, double* dce0, double* dCI, double* dci0,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
+int qpgpu_vjp_box_full(const qpgpu_problem_desc* d,
+                       const double* G, const double* CE,
+                       const double* x, const double* u, const int32_t* status,
+                       const double* gx, const double* gu, const double* gf,
+                       double* dG, double* dg0, double* dCE, double* dce0, double* dhi, double* dlo,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Name of the kernel a qpgpu_vjp_full / qpgpu_vjp_box_full launch of this shape runs: a name
+ * containing "full", and "lane" for n <= 8, "group" for 8 < n <= 64, "ws" for 64 < n <= 256; "" for
+ * n > 256 or n <= 0. */
+const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t p, int32_t m);
 
 /* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each

@@ -29,6 +29,14 @@ struct VjpArgs {
   double* dlo;   // box only
 };
 
+// The argument block of the full form (qpgpu_vjp_full / qpgpu_vjp_box_full).  The two cotangents sit
+// in a block of its own: the x-only kernels keep the kernel argument they had, byte for byte (the
+// register allocation of qp_vjp_ws.hip's kernel moved with the argument's size alone).
+struct VjpFullArgs : VjpArgs {
+  const double* gu;  // dl/du in the layout of u; may be NULL
+  const double* gf;  // dl/df, one double per QP in either layout; may be NULL
+};
+
 }  // namespace qpk
 
 // The kernel a launch of this n runs: NULL for n outside [1, 64].
@@ -36,6 +44,9 @@ extern "C" const char* qpk_vjp_name(int n);
 // Enqueue the backward step of QPs [0, a->batch) on `stream`; tiled != 0: QPGPU_LAYOUT_TILED64.
 // n outside [1, 64] is hipErrorInvalidValue.
 extern "C" hipError_t qpk_launch_vjp(const qpk::VjpArgs* a, int tiled, hipStream_t stream);
+// The same two for the full form.
+extern "C" const char* qpk_vjp_full_name(int n);
+extern "C" hipError_t qpk_launch_vjp_full(const qpk::VjpFullArgs* a, int tiled, hipStream_t stream);
 
 // qp_vjp_ws.hip, 64 < n <= 256 (include/qpgpu.h qpgpu_vjp_ws / qpgpu_vjp_box_ws).
 // The kernel a launch of this n runs: NULL for n outside [65, 256].
@@ -46,3 +57,7 @@ extern "C" int64_t qpk_vjp_ws_doubles(int n);
 // s working in ws[s * doubles, (s + 1) * doubles) on the QPs s, s + slots, ...  n outside [65, 256], a
 // NULL ws or slots < 1 is hipErrorInvalidValue.
 extern "C" hipError_t qpk_launch_vjp_ws(const qpk::VjpArgs* a, int tiled, void* ws, int64_t slots, hipStream_t stream);
+// The same two for the full form (qp_vjp_ws_full.hip: qp_vjp_ws.hip built a second time).
+extern "C" const char* qpk_vjp_ws_full_name(int n);
+extern "C" hipError_t qpk_launch_vjp_ws_full(const qpk::VjpFullArgs* a, int tiled, void* ws, int64_t slots,
+                                             hipStream_t stream);

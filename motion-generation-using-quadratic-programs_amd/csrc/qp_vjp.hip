@@ -35,6 +35,7 @@
 // no CI and writes no dCI.
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 #include "qp_common.h"
@@ -69,6 +70,29 @@ __device__ __forceinline__ double box_entry(int i, int j, int n) {
 
 constexpr int tri(int i, int k) { return i * (i + 1) / 2 + k; }
 
+// The full form (qpgpu_vjp_full) is every kernel below built a second time with
+// FULL = true, on VjpFullArgs: g.gu joins r before the q x q solve, g.gf turns c into ct and a into
+// ah in the outputs.  Each is a branch on the pointer, uniform over the launch, and a NULL pointer
+// leaves the other build's operations (no + 0.0 is added: it would turn a -0.0 into +0.0).  With
+// FULL = false nothing of it is compiled.
+template <bool FULL>
+using VjpArgsOf = std::conditional_t<FULL, VjpFullArgs, VjpArgs>;
+
+// a[i] as dG reads it: ah[i] = a[i] - hh * x[i], hh = 0.5 * gf
+template <bool FULL>
+__device__ __forceinline__ double vjp_ah(double a, double x, bool hasf, double hh) {
+  if constexpr (FULL)
+    if (hasf) return a - hh * x;
+  return a;
+}
+// dg0[i] = -(a[i] - gf * x[i])
+template <bool FULL>
+__device__ __forceinline__ double vjp_dg0(double a, double x, bool hasf, double gf) {
+  if constexpr (FULL)
+    if (hasf) return -(a - gf * x);
+  return -a;
+}
+
 // ---- one QP per lane ----------------------------------------------------------------------------
 template <int N>
 __device__ __forceinline__ void lane_fsub(const double (&L)[N * (N + 1) / 2], double (&v)[N]) {
@@ -87,11 +111,14 @@ __device__ __forceinline__ void lane_fsub(const double (&L)[N * (N + 1) / 2], do
 #define WS(t) Ws[(t) * 64 + lane]
 
 // The arithmetic of QP b in one lane, L holding the lower triangle of its G: a into w, x into xv, c
-// into the lane's Cs slots; the QP's mode (anything but kVjpOk: nothing was computed).  Ms, Ss, Cs,
-// Ws: the wave's LDS arrays.
-template <int T, int N, bool BOX>
-__device__ __forceinline__ int lane_solve(const VjpArgs& g, int64_t b, int lane, double* Ms, double* Ss, double* Cs,
-                                          int* Ws, double (&L)[N * (N + 1) / 2], double (&w)[N], double (&xv)[N]) {
+// into the lane's Cs slots (FULL with gf: ct = c + gfv * lam, once y is formed from c); the QP's
+// mode (anything but kVjpOk: nothing was computed).  Ms, Ss, Cs, Ws: the wave's LDS arrays; Lam
+// (FULL only): a slot per position for lam(t).  gl(t) and lam(t) are fetched with column t, so their
+// latency is the columns': gl(t) waits in the Cs slot that r[t] takes over.
+template <int T, int N, bool BOX, bool FULL>
+__device__ __forceinline__ int lane_solve(const VjpArgsOf<FULL>& g, int64_t b, int lane, double* Ms, double* Ss, double* Cs,
+                                          int* Ws, double (&L)[N * (N + 1) / 2], double (&w)[N], double (&xv)[N],
+                                          double gfv, double* Lam) {
   const int p = g.p, m = g.m;
   if (g.status && g.status[b] != QPGPU_QP_OK) return kVjpZero;
   const double* up = (p + m > 0) ? g.u + qbase<T>(b, p + m) : g.x;  // (never read with p + m == 0)
@@ -137,6 +164,11 @@ __device__ __forceinline__ int lane_solve(const VjpArgs& g, int64_t b, int lane,
   const int64_t qCE = qbase<T>(b, N * p), qCI = BOX ? 0 : qbase<T>(b, N * m);
   for (int t = 0; t < nq; t++) {
     double col[N];
+    if constexpr (FULL) {
+      const int64_t e = (int64_t)(t < p ? t : p + WS(t)) * T;  // position t's entry of u and of gu
+      if (g.gu) CS(t) = g.gu[qbase<T>(b, p + m) + e];
+      if (g.gf) Lam[t * 64 + lane] = up[e];
+    }
     if (t < p) {
 #pragma unroll
       for (int i = 0; i < N; i++) col[i] = g.CE[qCE + ((int64_t)i * p + t) * T];
@@ -165,6 +197,9 @@ __device__ __forceinline__ int lane_solve(const VjpArgs& g, int64_t b, int lane,
     double acc = 0.0;
 #pragma unroll
     for (int i = 0; i < N; i++) acc = acc + MS(i, s) * w[i];
+    if constexpr (FULL) {
+      if (g.gu) acc = acc + CS(s);  // gl(s), once, after the sum
+    }
     CS(s) = acc;
   }
   // R = chol(S), in place
@@ -203,11 +238,16 @@ __device__ __forceinline__ int lane_solve(const VjpArgs& g, int64_t b, int lane,
     for (int k = i + 1; k < N; k++) s = s - L[tri(k, i)] * w[k];
     w[i] = s / L[tri(i, i)];
   }
+  if constexpr (FULL) {
+    if (g.gf) {
+      for (int t = 0; t < nq; t++) CS(t) = CS(t) + gfv * Lam[t * 64 + lane];
+    }
+  }
   return kVjpOk;  // (w is a)
 }
 
-template <int T, int N, bool BOX>
-__global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgs g) {
+template <int T, int N, bool BOX, bool FULL>
+__global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgsOf<FULL> g) {
   constexpr int NT = N * (N + 1) / 2;
   __shared__ double Ls[(N * N + NT) * 64];  // M, then S; once a and c are known, the staging buffer of the QP-major stores
   __shared__ double Cs[N * 64];
@@ -230,7 +270,19 @@ __global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgs g) {
 #pragma unroll
       for (int k = 0; k <= i; k++) L[tri(i, k)] = Gp[(int64_t)(i * N + k) * T];
   }
-  const int mode = live ? lane_solve<T, N, BOX>(g, b, lane, Ms, Ss, Cs, Ws, L, w, xv) : kVjpDead;
+  bool hasf = false;
+  double gfv = 0.0, hh = 0.0;
+  double* Lam = nullptr;
+  if constexpr (FULL) {
+    __shared__ double Lams[N * 64];
+    Lam = Lams;
+    hasf = g.gf != nullptr;
+    if (hasf && live) {
+      gfv = g.gf[b];
+      hh = 0.5 * gfv;
+    }
+  }
+  const int mode = live ? lane_solve<T, N, BOX, FULL>(g, b, lane, Ms, Ss, Cs, Ws, L, w, xv, gfv, Lam) : kVjpDead;
   const bool ok = mode == kVjpOk;
   const double fv = mode == kVjpNaN ? __builtin_nan("") : 0.0;
   // (neither is read unless ok)
@@ -246,14 +298,16 @@ __global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgs g) {
     if (g.dg0) {
       double* o = g.dg0 + qbase<T>(b, N);
 #pragma unroll
-      for (int i = 0; i < N; i++) o[(int64_t)i * T] = -w[i];
+      for (int i = 0; i < N; i++) o[(int64_t)i * T] = vjp_dg0<FULL>(w[i], xv[i], hasf, gfv);
     }
     if (g.dG) {
       double* o = g.dG + qbase<T>(b, N * N);
 #pragma unroll
       for (int i = 0; i < N; i++)
 #pragma unroll
-        for (int j = 0; j < N; j++) o[(int64_t)(i * N + j) * T] = -0.5 * (w[i] * xv[j] + xv[i] * w[j]);
+        for (int j = 0; j < N; j++)
+          o[(int64_t)(i * N + j) * T] = -0.5 * (vjp_ah<FULL>(w[i], xv[i], hasf, hh) * xv[j] +
+                                                xv[i] * vjp_ah<FULL>(w[j], xv[j], hasf, hh));
     }
     if (g.dCE || g.dce0) {
       double* oc = g.dCE ? g.dCE + qbase<T>(b, N * p) : nullptr;
@@ -339,14 +393,17 @@ __global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgs g) {
     sg_sync();  // every lane is done with M and S
     if (g.dg0) {
 #pragma unroll
-      for (int i = 0; i < N; i++) buf[i * 65 + lane] = ok ? -w[i] : fv;
+      for (int i = 0; i < N; i++) buf[i * 65 + lane] = ok ? vjp_dg0<FULL>(w[i], xv[i], hasf, gfv) : fv;
       flush(g.dg0, N, 0, N);
     }
     if (g.dG) {
 #pragma unroll
       for (int i = 0; i < N; i++)
 #pragma unroll
-        for (int j = 0; j < N; j++) buf[(i * N + j) * 65 + lane] = ok ? -0.5 * (w[i] * xv[j] + xv[i] * w[j]) : fv;
+        for (int j = 0; j < N; j++)
+          buf[(i * N + j) * 65 + lane] = ok ? -0.5 * (vjp_ah<FULL>(w[i], xv[i], hasf, hh) * xv[j] +
+                                                      xv[i] * vjp_ah<FULL>(w[j], xv[j], hasf, hh))
+                                            : fv;
       flush(g.dG, N * N, 0, N * N);
     }
     emit(g.dCE, N, p, [&](int, int k, double ai, double xi) {
@@ -461,8 +518,8 @@ __device__ __forceinline__ double group_bsub(const double* A, int size, int boun
   return out;
 }
 
-template <int T, int S, bool BOX>
-__global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgs g) {
+template <int T, int S, bool BOX, bool FULL>
+__global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgsOf<FULL> g) {
   extern __shared__ double vjp_lds[];
   constexpr int LD = S + 1;
   const int lane = threadIdx.x, sub = lane / S, sl = lane % S, base = sub * S;
@@ -534,6 +591,9 @@ __global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgs g) {
       Sm[sl * LD + t] = acc;
     }
     for (int i = 0; i < n; i++) rr = rr + Mm[i * LD + sl] * Mm[i * LD + nq];
+    if constexpr (FULL) {
+      if (g.gu) rr = rr + g.gu[qbase<T>(b, p + m) + (int64_t)(sl < p ? sl : p + wi[sl]) * T];  // gl(s)
+    }
   }
   sg_sync();
   group_chol<S>(Sm, nq, n, sl, base);
@@ -549,18 +609,30 @@ __global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgs g) {
   }
   const double ai = group_bsub<S>(Lm, n, n, sl, y, zv);
   if (sl < n) av[sl] = ai;
+  bool hasf = false;
+  double gfv = 0.0, hh = 0.0;
+  if constexpr (FULL) {
+    hasf = g.gf != nullptr;
+    if (hasf) {
+      gfv = g.gf[b];
+      hh = 0.5 * gfv;
+      // ct = c + gf * lam for the outputs (y, formed from c, is behind the barriers of bsub)
+      if (sl < nq) cv[sl] = c + gfv * (sl < p ? up[(int64_t)sl * T] : uip[(int64_t)wi[sl] * T]);
+    }
+  }
   sg_sync();
 
   if (mode != kVjpOk) {
     vjp_fill<T>(g, b, mode == kVjpZero ? 0.0 : __builtin_nan(""), sl, S);
     return;
   }
-  if (g.dg0 && sl < n) g.dg0[qbase<T>(b, n) + (int64_t)sl * T] = -ai;
+  if (g.dg0 && sl < n) g.dg0[qbase<T>(b, n) + (int64_t)sl * T] = vjp_dg0<FULL>(ai, xs[sl], hasf, gfv);
   if (g.dG) {
     double* o = g.dG + qG;
     for (int e = sl; e < n * n; e += S) {
       const int i = e / n, j = e % n;
-      o[(int64_t)e * T] = -0.5 * (av[i] * xs[j] + xs[i] * av[j]);
+      o[(int64_t)e * T] = -0.5 * (vjp_ah<FULL>(av[i], xs[i], hasf, hh) * xs[j] +
+                                  xs[i] * vjp_ah<FULL>(av[j], xs[j], hasf, hh));
     }
   }
   if (g.dCE) {
@@ -605,41 +677,79 @@ __global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgs g) {
   }
 }
 
-using VjpKernel = void (*)(VjpArgs);
+template <bool FULL>
+using VjpKernel = void (*)(VjpArgsOf<FULL>);
 
-template <int T, bool BOX>
-static VjpKernel lane_kernel_of(int n) {
+template <int T, bool BOX, bool FULL>
+static VjpKernel<FULL> lane_kernel_of(int n) {
   switch (n) {
-    case 1: return vjp_lane_kernel<T, 1, BOX>;
-    case 2: return vjp_lane_kernel<T, 2, BOX>;
-    case 3: return vjp_lane_kernel<T, 3, BOX>;
-    case 4: return vjp_lane_kernel<T, 4, BOX>;
-    case 5: return vjp_lane_kernel<T, 5, BOX>;
-    case 6: return vjp_lane_kernel<T, 6, BOX>;
-    case 7: return vjp_lane_kernel<T, 7, BOX>;
-    default: return vjp_lane_kernel<T, 8, BOX>;
+    case 1: return vjp_lane_kernel<T, 1, BOX, FULL>;
+    case 2: return vjp_lane_kernel<T, 2, BOX, FULL>;
+    case 3: return vjp_lane_kernel<T, 3, BOX, FULL>;
+    case 4: return vjp_lane_kernel<T, 4, BOX, FULL>;
+    case 5: return vjp_lane_kernel<T, 5, BOX, FULL>;
+    case 6: return vjp_lane_kernel<T, 6, BOX, FULL>;
+    case 7: return vjp_lane_kernel<T, 7, BOX, FULL>;
+    default: return vjp_lane_kernel<T, 8, BOX, FULL>;
   }
 }
 
-template <int T, bool BOX>
-static VjpKernel group_kernel_of(int n) {
-  return n <= 16 ? vjp_group_kernel<T, 16, BOX> : n <= 32 ? vjp_group_kernel<T, 32, BOX> : vjp_group_kernel<T, 64, BOX>;
+template <int T, bool BOX, bool FULL>
+static VjpKernel<FULL> group_kernel_of(int n) {
+  return n <= 16   ? vjp_group_kernel<T, 16, BOX, FULL>
+         : n <= 32 ? vjp_group_kernel<T, 32, BOX, FULL>
+                   : vjp_group_kernel<T, 64, BOX, FULL>;
 }
 
 // Dynamic LDS beyond 64 KiB is granted once per kernel and device; host threads may launch
 // concurrently (include/qpgpu.h), so the record is locked.
-static hipError_t grant_lds(VjpKernel k, size_t bytes) {
+static hipError_t grant_lds(const void* k, size_t bytes) {
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> granted;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  const std::pair<const void*, int> key(reinterpret_cast<const void*>(k), dev);
+  const std::pair<const void*, int> key(k, dev);
   std::lock_guard<std::mutex> lk(mu);
   if (granted.count(key)) return hipSuccess;
   e = hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e == hipSuccess) granted.insert(key);
   return e;
+}
+
+template <bool FULL>
+static hipError_t launch_vjp(const VjpArgsOf<FULL>* a, int tiled, hipStream_t stream) {
+  const int n = a->n;
+  if (n < 1 || n > 64) return hipErrorInvalidValue;
+  const bool lane = n <= 8, box = a->box != 0;
+  VjpKernel<FULL> k;
+  if (lane)
+    k = tiled ? (box ? lane_kernel_of<64, true, FULL>(n) : lane_kernel_of<64, false, FULL>(n))
+              : (box ? lane_kernel_of<1, true, FULL>(n) : lane_kernel_of<1, false, FULL>(n));
+  else
+    k = tiled ? (box ? group_kernel_of<64, true, FULL>(n) : group_kernel_of<64, false, FULL>(n))
+              : (box ? group_kernel_of<1, true, FULL>(n) : group_kernel_of<1, false, FULL>(n));
+  const int S = n <= 16 ? 16 : n <= 32 ? 32 : 64;
+  const int64_t per_wg = lane ? 64 : 64 / S;  // QPs per workgroup (one wavefront)
+  size_t lds = 0;
+  if (!lane) {
+    const int per = S == 16 ? vjp_group_doubles<16>() : S == 32 ? vjp_group_doubles<32>() : vjp_group_doubles<64>();
+    lds = (size_t)per * (64 / S) * sizeof(double);
+    if (lds > 65536) {  // S = 64: beyond the default limit, inside the CU's 160 KiB
+      const hipError_t e = grant_lds(reinterpret_cast<const void*>(k), lds);
+      if (e != hipSuccess) return e;
+    }
+  }
+  VjpArgsOf<FULL> c = *a;
+  const int64_t per = (int64_t)1 << 30;  // workgroups per launch: the grid stays inside 32 bits
+  for (int64_t w0 = 0; w0 * per_wg < a->batch; w0 += per) {
+    c.qp0 = w0 * per_wg;
+    const int64_t left = (a->batch - c.qp0 + per_wg - 1) / per_wg;
+    hipLaunchKernelGGL(k, dim3((unsigned)(left < per ? left : per)), dim3(64), lds, stream, c);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace qpk
@@ -652,37 +762,18 @@ extern "C" const char* qpk_vjp_name(int n) {
   return n <= 16 ? "vjp_group_s16" : n <= 32 ? "vjp_group_s32" : "vjp_group_s64";
 }
 
+extern "C" const char* qpk_vjp_full_name(int n) {
+  static const char* const lane[] = {"vjp_full_lane_n1", "vjp_full_lane_n2", "vjp_full_lane_n3", "vjp_full_lane_n4",
+                                     "vjp_full_lane_n5", "vjp_full_lane_n6", "vjp_full_lane_n7", "vjp_full_lane_n8"};
+  if (n < 1 || n > 64) return nullptr;
+  if (n <= 8) return lane[n - 1];
+  return n <= 16 ? "vjp_full_group_s16" : n <= 32 ? "vjp_full_group_s32" : "vjp_full_group_s64";
+}
+
 extern "C" hipError_t qpk_launch_vjp(const qpk::VjpArgs* a, int tiled, hipStream_t stream) {
-  using namespace qpk;
-  const int n = a->n;
-  if (n < 1 || n > 64) return hipErrorInvalidValue;
-  const bool lane = n <= 8, box = a->box != 0;
-  VjpKernel k;
-  if (lane)
-    k = tiled ? (box ? lane_kernel_of<64, true>(n) : lane_kernel_of<64, false>(n))
-              : (box ? lane_kernel_of<1, true>(n) : lane_kernel_of<1, false>(n));
-  else
-    k = tiled ? (box ? group_kernel_of<64, true>(n) : group_kernel_of<64, false>(n))
-              : (box ? group_kernel_of<1, true>(n) : group_kernel_of<1, false>(n));
-  const int S = n <= 16 ? 16 : n <= 32 ? 32 : 64;
-  const int64_t per_wg = lane ? 64 : 64 / S;  // QPs per workgroup (one wavefront)
-  size_t lds = 0;
-  if (!lane) {
-    const int per = S == 16 ? vjp_group_doubles<16>() : S == 32 ? vjp_group_doubles<32>() : vjp_group_doubles<64>();
-    lds = (size_t)per * (64 / S) * sizeof(double);
-    if (lds > 65536) {  // S = 64: beyond the default limit, inside the CU's 160 KiB
-      const hipError_t e = grant_lds(k, lds);
-      if (e != hipSuccess) return e;
-    }
-  }
-  VjpArgs c = *a;
-  const int64_t per = (int64_t)1 << 30;  // workgroups per launch: the grid stays inside 32 bits
-  for (int64_t w0 = 0; w0 * per_wg < a->batch; w0 += per) {
-    c.qp0 = w0 * per_wg;
-    const int64_t left = (a->batch - c.qp0 + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(k, dim3((unsigned)(left < per ? left : per)), dim3(64), lds, stream, c);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return qpk::launch_vjp<false>(a, tiled, stream);
+}
+
+extern "C" hipError_t qpk_launch_vjp_full(const qpk::VjpFullArgs* a, int tiled, hipStream_t stream) {
+  return qpk::launch_vjp<true>(a, tiled, stream);
 }

@@ -29,12 +29,29 @@
 //              subtractions, so z[i] needs no broadcast: one barrier per row.
 // Every barrier sits in control flow uniform over the workgroup: the QP loop, the masked-QP skip
 // and the q > n case depend on the QP alone.
+//
+// The full form (qpgpu_vjp_full) is this file built a second time, by
+// qp_vjp_ws_full.hip with QPGPU_VJP_FULL = 1, on VjpFullArgs: g.gu joins r after ws_gram's sum, g.gf
+// turns c into ct and a into ah in the outputs.  Each is a branch on the pointer, uniform over the
+// launch, and a NULL pointer leaves this build's operations (no + 0.0 is added: it would turn a -0.0
+// into +0.0).  Without the macro the translation unit is the text it was.
 #include "qp_common.h"
 #include "qp_vjp.h"
+
+#ifndef QPGPU_VJP_FULL
+#define QPGPU_VJP_FULL 0
+#endif
 
 namespace qpk {
 
 namespace {
+
+#if QPGPU_VJP_FULL
+using WsArgs = VjpFullArgs;
+#define vjp_ws_kernel vjp_ws_full_kernel
+#else
+using WsArgs = VjpArgs;
+#endif
 
 constexpr int kWsLanes = 256;
 constexpr int kJB = 8;     // columns of a factorisation panel
@@ -46,7 +63,7 @@ static_assert(kScratch >= kWsLanes * kJB + kJB * (kJB + 1), "chol: pivot rows + 
 static_assert(kScratch >= kIB * kCP, "S: rows of M");
 
 struct VjpWsArgs {
-  VjpArgs g;
+  WsArgs g;
   double* ws;
   int64_t per;  // doubles per slot
 };
@@ -289,7 +306,7 @@ __global__ void __launch_bounds__(kWsLanes) vjp_ws_kernel(VjpWsArgs w) {
   __shared__ double xs[kWsLanes], av[kWsLanes], cv[kWsLanes], rv[kWsLanes], dg[kWsLanes], pb[2 * kWsLanes], zb[2];
   __shared__ int wi[kWsLanes];
   __shared__ int cnt[2][kWsLanes / 64];
-  const VjpArgs& g = w.g;
+  const WsArgs& g = w.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = g.n, p = g.p, m = g.m, ldm = n + 1;
   double* const Lc = w.ws + (int64_t)blockIdx.x * w.per;
@@ -354,7 +371,13 @@ __global__ void __launch_bounds__(kWsLanes) vjp_ws_kernel(VjpWsArgs w) {
     ws_fsub_columns(Lc, n, Mw, ldm, C, scratch, tid);
     ws_gram(Mw, ldm, n, q, Sc, n, rv, scratch, tid);
     ws_chol([&](int i, int j) { return Sc[(int64_t)j * n + i]; }, Sc, n, q, scratch, tid);
+#if QPGPU_VJP_FULL
+    double rr = tid < q ? rv[tid] : 0.0;  // gl(t) is added once, after ws_gram's sum
+    if (g.gu && tid < q) rr = rr + g.gu[qbase<T>(b, p + m) + (int64_t)(tid < p ? tid : p + wi[tid]) * T];
+    const double f = ws_fsub_vector(Sc, n, q, rr, zb, tid);
+#else
     const double f = ws_fsub_vector(Sc, n, q, tid < q ? rv[tid] : 0.0, zb, tid);
+#endif
     ws_bsub_vector(Sc, n, q, f, cv, dg, pb, tid);
     // lane i: y_i = w_i - sum_t M[i][t] c[t], then a = bsub(L, y)
     double y = 0.0;
@@ -365,15 +388,35 @@ __global__ void __launch_bounds__(kWsLanes) vjp_ws_kernel(VjpWsArgs w) {
     }
     ws_bsub_vector(Lc, n, n, y, av, dg, pb, tid);
 
+#if QPGPU_VJP_FULL
+    const bool hasf = g.gf != nullptr;  // (uniform)
+    double gfv = 0.0, hh = 0.0;
+    if (hasf) {
+      gfv = g.gf[b];
+      hh = 0.5 * gfv;
+      // ct = c + gf * lam for the outputs (y is formed, and a barrier lies behind it)
+      if (tid < q) cv[tid] = cv[tid] + gfv * (tid < p ? up[(int64_t)tid * T] : uip[(int64_t)wi[tid] * T]);
+      __syncthreads();
+    }
+#endif
     if (g.dg0) {
       double* o = g.dg0 + qbase<T>(b, n);
+#if QPGPU_VJP_FULL
+      if (tid < n) o[(int64_t)tid * T] = hasf ? -(av[tid] - gfv * xs[tid]) : -av[tid];
+#else
       if (tid < n) o[(int64_t)tid * T] = -av[tid];
+#endif
     }
     if (g.dG) {
       double* o = g.dG + qG;
       for (int e = tid; e < n * n; e += kWsLanes) {
         const int i = e / n, j = e - i * n;
+#if QPGPU_VJP_FULL
+        const double ahi = hasf ? av[i] - hh * xs[i] : av[i], ahj = hasf ? av[j] - hh * xs[j] : av[j];
+        o[(int64_t)e * T] = -0.5 * (ahi * xs[j] + xs[i] * ahj);
+#else
         o[(int64_t)e * T] = -0.5 * (av[i] * xs[j] + xs[i] * av[j]);
+#endif
       }
     }
     if (g.dCE) {
@@ -431,6 +474,26 @@ __global__ void __launch_bounds__(kWsLanes) vjp_ws_kernel(VjpWsArgs w) {
 
 }  // namespace qpk
 
+#if QPGPU_VJP_FULL
+#undef vjp_ws_kernel
+
+extern "C" const char* qpk_vjp_ws_full_name(int n) { return (n > 64 && n <= 256) ? "vjp_full_ws_g256" : nullptr; }
+
+extern "C" hipError_t qpk_launch_vjp_ws_full(const qpk::VjpFullArgs* a, int tiled, void* ws, int64_t slots,
+                                             hipStream_t stream) {
+  using namespace qpk;
+  if (!qpk_vjp_ws_name(a->n) || !ws || slots < 1) return hipErrorInvalidValue;
+  if (slots > a->batch) slots = a->batch;
+  if (slots > ((int64_t)1 << 30)) slots = (int64_t)1 << 30;  // the grid stays inside 32 bits
+  VjpWsArgs w = {*a, static_cast<double*>(ws), qpk_vjp_ws_doubles(a->n)};
+  w.g.qp0 = 0;
+  const bool box = a->box != 0;
+  void (*k)(VjpWsArgs) = tiled ? (box ? vjp_ws_full_kernel<64, true> : vjp_ws_full_kernel<64, false>)
+                               : (box ? vjp_ws_full_kernel<1, true> : vjp_ws_full_kernel<1, false>);
+  hipLaunchKernelGGL(k, dim3((unsigned)slots), dim3(kWsLanes), 0, stream, w);
+  return hipGetLastError();
+}
+#else
 extern "C" const char* qpk_vjp_ws_name(int n) { return (n > 64 && n <= 256) ? "vjp_ws_g256" : nullptr; }
 
 extern "C" int64_t qpk_vjp_ws_doubles(int n) { return (n > 64 && n <= 256) ? 3 * (int64_t)n * n + n : 0; }
@@ -448,3 +511,4 @@ extern "C" hipError_t qpk_launch_vjp_ws(const qpk::VjpArgs* a, int tiled, void* 
   hipLaunchKernelGGL(k, dim3((unsigned)slots), dim3(kWsLanes), 0, stream, w);
   return hipGetLastError();
 }
+#endif

@@ -570,7 +570,8 @@ static bool vjp_sizes_fit(const qpgpu_problem_desc* d) {
 static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
                    const double* CI, const double* x, const double* u, const int32_t* status,
                    const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
-                   double* dci0, double* dhi, double* dlo, void* stream) {
+                   double* dci0, double* dhi, double* dlo, void* stream, bool full = false,
+                   const double* gu = nullptr, const double* gf = nullptr) {
   const int rc = vjp_rules(d, box, G, CE, CI, x, u, gx);
   if (rc) return rc;
   // n <= 64: L, M and S of a QP fit on chip
@@ -579,7 +580,14 @@ static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const
   qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
                     dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
                     box ? dlo : nullptr};
-  const hipError_t e = qpk_launch_vjp(&a, d->layout == QPGPU_LAYOUT_TILED64, reinterpret_cast<hipStream_t>(stream));
+  const int tiled = d->layout == QPGPU_LAYOUT_TILED64;
+  hipError_t e;
+  if (full) {
+    const qpk::VjpFullArgs fa = {a, gu, gf};
+    e = qpk_launch_vjp_full(&fa, tiled, reinterpret_cast<hipStream_t>(stream));
+  } else {
+    e = qpk_launch_vjp(&a, tiled, reinterpret_cast<hipStream_t>(stream));
+  }
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
   return QPGPU_SUCCESS;
 }
@@ -610,11 +618,11 @@ static int vjp_ws_run(const qpgpu_problem_desc* d, bool box, const double* G, co
                       const double* CI, const double* x, const double* u, const int32_t* status,
                       const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
                       double* dci0, double* dhi, double* dlo, void* workspace, int64_t workspace_bytes,
-                      void* stream) {
+                      void* stream, bool full = false, const double* gu = nullptr, const double* gf = nullptr) {
   const int rc = vjp_rules(d, box, G, CE, CI, x, u, gx);
   if (rc) return rc;
   if (qpk_vjp_name(d->n))
-    return vjp_run(d, box, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, dhi, dlo, stream);
+    return vjp_run(d, box, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, dhi, dlo, stream, full, gu, gf);
   if (!qpk_vjp_ws_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   if (d->batch == 0) return QPGPU_SUCCESS;
   const int64_t per = qpk_vjp_ws_doubles(d->n) * (int64_t)sizeof(double);
@@ -623,8 +631,14 @@ static int vjp_ws_run(const qpgpu_problem_desc* d, bool box, const double* G, co
   qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
                     dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
                     box ? dlo : nullptr};
-  const hipError_t e = qpk_launch_vjp_ws(&a, d->layout == QPGPU_LAYOUT_TILED64, workspace, workspace_bytes / per,
-                                         reinterpret_cast<hipStream_t>(stream));
+  const int tiled = d->layout == QPGPU_LAYOUT_TILED64;
+  hipError_t e;
+  if (full) {
+    const qpk::VjpFullArgs fa = {a, gu, gf};
+    e = qpk_launch_vjp_ws_full(&fa, tiled, workspace, workspace_bytes / per, reinterpret_cast<hipStream_t>(stream));
+  } else {
+    e = qpk_launch_vjp_ws(&a, tiled, workspace, workspace_bytes / per, reinterpret_cast<hipStream_t>(stream));
+  }
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
   return QPGPU_SUCCESS;
 }
@@ -660,6 +674,33 @@ const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t p, int32_t m) {
   (void)m;
   const char* k = qpk_vjp_name(n);
   if (!k) k = qpk_vjp_ws_name(n);
+  return k ? k : "";
+}
+
+// ---- the full backward step: cotangents on u and f too ----------------------------
+// The rules and the workspace semantics are vjp_ws_run's; gu and gf may each be NULL.  The kernels
+// are the FULL builds of the same sources.
+int qpgpu_vjp_full(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* CI,
+                   const double* x, const double* u, const int32_t* status, const double* gx,
+                   const double* gu, const double* gf, double* dG, double* dg0, double* dCE, double* dce0,
+                   double* dCI, double* dci0, void* workspace, int64_t workspace_bytes, void* stream) {
+  return vjp_ws_run(d, false, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, nullptr, nullptr,
+                    workspace, workspace_bytes, stream, true, gu, gf);
+}
+
+int qpgpu_vjp_box_full(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* x,
+                       const double* u, const int32_t* status, const double* gx, const double* gu,
+                       const double* gf, double* dG, double* dg0, double* dCE, double* dce0, double* dhi,
+                       double* dlo, void* workspace, int64_t workspace_bytes, void* stream) {
+  return vjp_ws_run(d, true, G, CE, nullptr, x, u, status, gx, dG, dg0, dCE, dce0, nullptr, nullptr, dhi, dlo,
+                    workspace, workspace_bytes, stream, true, gu, gf);
+}
+
+const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t p, int32_t m) {
+  (void)p;
+  (void)m;
+  const char* k = qpk_vjp_full_name(n);
+  if (!k) k = qpk_vjp_ws_full_name(n);
   return k ? k : "";
 }
 

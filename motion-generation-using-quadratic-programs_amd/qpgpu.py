@@ -80,6 +80,9 @@ EXPORTED_SYMBOLS = (
     "qpgpu_vjp_ws",
     "qpgpu_vjp_box_ws",
     "qpgpu_kernel_name_vjp_ws",
+    "qpgpu_vjp_full",
+    "qpgpu_vjp_box_full",
+    "qpgpu_kernel_name_vjp_full",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -152,6 +155,12 @@ def _load():
     lib.qpgpu_vjp_box_ws.restype = ctypes.c_int
     lib.qpgpu_kernel_name_vjp_ws.argtypes = [ctypes.c_int32] * 3
     lib.qpgpu_kernel_name_vjp_ws.restype = ctypes.c_char_p
+    lib.qpgpu_vjp_full.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 15 + [vp, ctypes.c_int64, vp]
+    lib.qpgpu_vjp_full.restype = ctypes.c_int
+    lib.qpgpu_vjp_box_full.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 14 + [vp, ctypes.c_int64, vp]
+    lib.qpgpu_vjp_box_full.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_vjp_full.argtypes = [ctypes.c_int32] * 3
+    lib.qpgpu_kernel_name_vjp_full.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -240,6 +249,12 @@ def kernel_name_vjp_ws(n: int, p: int = 0, m: int = 0) -> str:
     """The kernel a qpgpu_vjp_ws / qpgpu_vjp_box_ws launch of this shape runs: kernel_name_vjp's for
     n <= 64, a "ws" name for 64 < n <= 256, "" beyond (QPGPU_ERR_UNSUPPORTED_SHAPE)."""
     return LIB.qpgpu_kernel_name_vjp_ws(n, p, m).decode()
+
+
+def kernel_name_vjp_full(n: int, p: int = 0, m: int = 0) -> str:
+    """The kernel a qpgpu_vjp_full / qpgpu_vjp_box_full launch of this shape runs: a name with "full"
+    in it, and "lane" for n <= 8, "group" for 8 < n <= 64, "ws" for 64 < n <= 256; "" beyond."""
+    return LIB.qpgpu_kernel_name_vjp_full(n, p, m).decode()
 
 
 def vjp_workspace_bytes(n: int, p: int, m: int, slots: int) -> int:
@@ -638,7 +653,8 @@ class _DeviceBatchBase:
         n, p, m = self.n, self.p, self.m
         return {"dG": n * n, "dg0": n, "dCE": n * p, "dce0": p, "dCI": n * m, "dci0": m, "dhi": n, "dlo": n}[name]
 
-    def vjp(self, u, gx, outs=None, status=True, stream=None, x=None, slots=VJP_SLOTS, workspace=None):
+    def vjp(self, u, gx, outs=None, status=True, stream=None, x=None, slots=VJP_SLOTS, workspace=None,
+            gu=None, gf=None):
         """Enqueue the backward step (qpgpu_vjp / qpgpu_vjp_box, include/qpgpu.h) of this batch's
         resident inputs at (x, u) for gx = dl/dx on `stream` (default current): no host round
         trip, so it can follow a dual solve on the same stream.  u as kkt_residuals() takes it; gx:
@@ -650,7 +666,9 @@ class _DeviceBatchBase:
         computed.  Returns the dict of the tensors written, each (rows, E) in this batch's layout
         (vjp_rows() decodes host copies).  For n > 64 the call goes to qpgpu_vjp_ws /
         qpgpu_vjp_box_ws with `workspace` (a uint8 tensor; default: a new one of min(batch, slots)
-        slots, which the results do not depend on); for n <= 64 both are ignored."""
+        slots, which the results do not depend on); for n <= 64 both are ignored.  gu (dl/du, laid out
+        like u) and gf (dl/df, one float64 per QP in either layout): with either given the call
+        goes to qpgpu_vjp_full / qpgpu_vjp_box_full, the backward step of a loss l(x, u, f)."""
         import torch
 
         x = self.x if x is None else x
@@ -667,11 +685,20 @@ class _DeviceBatchBase:
         d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
         vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         tensors = [getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st, gx] + [outs.get(k) for k in self._VJP_OUTPUTS]
+        full = gu is not None or gf is not None
+        if full:
+            k = len(self._VJP_INPUTS) + 4
+            tensors[k:k] = [gu, gf]
         if self.n <= VJP_ON_CHIP_N:
+            if full:
+                entry = self._ENTRY_VJP + "_full"
+                _check(getattr(LIB, entry)(ctypes.byref(d), *[vp(t) for t in tensors], None, 0,
+                                           ctypes.c_void_p(stream.cuda_stream)), entry)
+                return outs
             _check(getattr(LIB, self._ENTRY_VJP)(ctypes.byref(d), *[vp(t) for t in tensors],
                                                  ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_VJP)
             return outs
-        entry = self._ENTRY_VJP + "_ws"
+        entry = self._ENTRY_VJP + ("_full" if full else "_ws")
         if workspace is None:
             with torch.cuda.stream(stream):
                 workspace = _vjp_workspace(self.n, self.p, self.m, self.batch, slots, x.device)
@@ -923,7 +950,7 @@ def kkt_residuals(pr, x, u, status=None, layout=None, device="cuda:0"):
     return db.kkt_rows(r)
 
 
-def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slots=VJP_SLOTS):
+def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slots=VJP_SLOTS, gu=None, gf=None):
     """The gradients of l with respect to the data of every QP of `pr` (Problems: qpgpu_vjp;
     BoxProblems: qpgpu_vjp_box) at the primal-dual pair (x, u) for gx = dl/dx, computed on the GPU:
     a dict of float64 arrays shaped like the inputs — dG (B, n, n), dg0 (B, n), dCE (B, n, p),
@@ -931,7 +958,9 @@ def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slot
     x and gx are (B, n), u is (B, p + m) in QP-major order (may be None when p + m == 0); with
     `status` (B int32) a QP that is not QP_OK gets +0.0 everywhere.  outs: the names to compute
     (default all six).  layout="tiled64" runs the TILED64 form (converted here on the host).  For
-    n > 64 the entries are qpgpu_vjp_ws / qpgpu_vjp_box_ws with a workspace of min(B, slots) slots."""
+    n > 64 the entries are qpgpu_vjp_ws / qpgpu_vjp_box_ws with a workspace of min(B, slots) slots.
+    gu (B, p + m) = dl/du and gf (B,) = dl/df: with either given the entries are qpgpu_vjp_full /
+    qpgpu_vjp_box_full, the backward step of a loss l(x, u, f)."""
     import torch
 
     db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
@@ -942,18 +971,22 @@ def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slot
     xd, gd = up(x, pr.n), up(gx, pr.n)
     ud = up(u, E) if E > 0 else None
     sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
-    res = db.vjp(ud, gd, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd, slots=slots)
+    gud = None if gu is None else up(gu, E)
+    gfd = None if gf is None else torch.from_numpy(np.array(gf, dtype=np.float64, order="C").reshape(B)).to(device)
+    res = db.vjp(ud, gd, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd, slots=slots,
+                 gu=gud, gf=gfd)
     torch.cuda.synchronize(xd.device)
     return db.vjp_rows(res)
 
 
 @functools.lru_cache(maxsize=None)
 def _layer_functions():
-    """The two torch.autograd.Functions behind qp_layer / qp_layer_box (built at first use: torch is
+    """The torch.autograd.Functions behind qp_layer / qp_layer_box and their _full forms, which also
+    return u, f and status and take their cotangents (built at first use: torch is
     imported lazily everywhere in this module)."""
     import torch
 
-    def run(box, ctx, G, g0, CE, ce0, c5, c6):
+    def run(box, ctx, G, g0, CE, ce0, c5, c6, full=False):
         B, n, p = G.shape[0], G.shape[-1], CE.shape[-1]
         m = 2 * n if box else c5.shape[-1]
         for t in (G, g0, CE, ce0, c5, c6):
@@ -973,9 +1006,13 @@ def _layer_functions():
                                    None, stream), entry)
         ctx.save_for_backward(ins[0], ins[2], ins[4], x, u, st)
         ctx.shape = (B, n, p, m)
+        if full:
+            ctx.mark_non_differentiable(st)
+            ctx.set_materialize_grads(False)
+            return x, u, f, st
         return x
 
-    def back(box, ctx, gx):
+    def back(box, ctx, gx, gu=None, gf=None, full=False):
         G, CE, c5, x, u, st = ctx.saved_tensors
         B, n, p, m = ctx.shape
         need = ctx.needs_input_grad
@@ -984,6 +1021,16 @@ def _layer_functions():
         d = ProblemDesc(n, p, m, 0, B, 0, LAYOUT_QP_MAJOR)
         vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(G.device).cuda_stream)
+        if full:  # one call to the full entry; an output the loss does not use arrives as None: NULL
+            gx = torch.zeros((B, n), dtype=torch.float64, device=G.device) if gx is None else gx.contiguous()
+            gu = None if gu is None else gu.contiguous()
+            gf = None if gf is None else gf.contiguous()
+            ins = (vp(G), vp(CE)) + (() if box else (vp(c5),)) + (vp(x), vp(u), vp(st), vp(gx), vp(gu), vp(gf))
+            entry = "qpgpu_vjp_box_full" if box else "qpgpu_vjp_full"
+            ws = _vjp_workspace(n, p, m, B, VJP_SLOTS, G.device) if n > VJP_ON_CHIP_N else None
+            _check(getattr(LIB, entry)(ctypes.byref(d), *ins, *[vp(t) for t in outs], vp(ws),
+                                       0 if ws is None else ws.numel(), stream), entry)
+            return tuple(outs)
         gx = gx.contiguous()
         ins = (vp(G), vp(CE)) + (() if box else (vp(c5),)) + (vp(x), vp(u), vp(st), vp(gx))
         entry = "qpgpu_vjp_box" if box else "qpgpu_vjp"
@@ -1014,7 +1061,25 @@ def _layer_functions():
         def backward(ctx, gx):
             return back(True, ctx, gx)
 
-    return QpLayer, QpLayerBox
+    class QpLayerFull(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, G, g0, CE, ce0, CI, ci0):
+            return run(False, ctx, G, g0, CE, ce0, CI, ci0, full=True)
+
+        @staticmethod
+        def backward(ctx, gx, gu, gf, gst):
+            return back(False, ctx, gx, gu, gf, full=True)
+
+    class QpLayerBoxFull(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, G, g0, CE, ce0, hi, lo):
+            return run(True, ctx, G, g0, CE, ce0, hi, lo, full=True)
+
+        @staticmethod
+        def backward(ctx, gx, gu, gf, gst):
+            return back(True, ctx, gx, gu, gf, full=True)
+
+    return QpLayer, QpLayerBox, QpLayerFull, QpLayerBoxFull
 
 
 def qp_layer(G, g0, CE, ce0, CI, ci0):
@@ -1033,6 +1098,23 @@ def qp_layer_box(G, g0, CE, ce0, hi, lo):
     """qp_layer for bounds lo <= x <= hi (hi, lo: (B, n)): qpgpu_solve_batched_box_dual forward,
     qpgpu_vjp_box backward."""
     return _layer_functions()[1].apply(G, g0, CE, ce0, hi, lo)
+
+
+def qp_layer_full(G, g0, CE, ce0, CI, ci0):
+    """qp_layer returning everything the dual solve does, (x, u, f, status): x (B, n), the
+    multipliers u (B, p + m), the optimal values f (B,) and the int32 status (B,), which carries no
+    gradient.  A loss may use any of x, u and f: backward is one call to qpgpu_vjp_full on the
+    current stream (n > 64: with a workspace from torch's caching allocator), an output the loss
+    does not use passed as NULL, so a graph that uses only x gets the bits of qp_layer's gradients.
+    No gradient flows through a QP whose status is not QP_OK, nor through the multiplier of an
+    inequality that is exactly 0 (include/qpgpu.h)."""
+    return _layer_functions()[2].apply(G, g0, CE, ce0, CI, ci0)
+
+
+def qp_layer_box_full(G, g0, CE, ce0, hi, lo):
+    """qp_layer_full for bounds lo <= x <= hi: u is (B, p + 2n), equalities, upper bounds, lower
+    bounds (qpgpu_solve_batched_box_dual forward, qpgpu_vjp_box_full backward)."""
+    return _layer_functions()[3].apply(G, g0, CE, ce0, hi, lo)
 
 
 def relayout(src, dst, batch: int, elems: int, to_tiled: bool, stream=None):

@@ -21,6 +21,16 @@ under the same protocol.
     python tools/vjp_cost.py [--reps 20] [--parent-lib PATH] [--out profiles/vjp_cost/vjp_cost.log]
     python tools/vjp_cost.py --shapes C5,ws100,ws65 --layouts qp_major --parent-lib PATH \
         --out profiles/vjp_ws_cost/vjp_ws_cost.log
+
+--full times the full backward step instead: (a) qpgpu_vjp_full with gu and gf given
+(standard normal), (b) the x-only entry (qpgpu_vjp, n > 64: qpgpu_vjp_ws) from the library under test
+and, with --parent-lib, (c) the same x-only entry launched from the parent's build, on the same
+QPs under the protocol above: every launch on the next resident set, the order of the kinds rotating
+from one repetition to the next.  The record carries the three medians and spreads and the
+ratios full / x-only and x-only / parent's x-only; n > 64 runs at the first slot count only.
+
+    python tools/vjp_cost.py --full --shapes C1,C2,mgqp,C3,n64,C5,ws100,ws65 --parent-lib PATH \
+        --out profiles/vjp_full/vjp_full_cost.log
 """
 import argparse
 import ctypes
@@ -53,6 +63,7 @@ def main():
     ap.add_argument("--layouts", default="qp_major,tiled64")
     ap.add_argument("--parent-lib", default=None, help="a libqpgpu.so of the parent commit for the dual solve")
     ap.add_argument("--slots", default="512,256,1024", help="n > 64: QPs in flight, the first is the headline")
+    ap.add_argument("--full", action="store_true", help="time qpgpu_vjp_full beside the x-only entry")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -63,6 +74,10 @@ def main():
         solve_lib = ctypes.CDLL(os.path.abspath(args.parent_lib), mode=os.RTLD_LOCAL | os.RTLD_NOW | os.RTLD_DEEPBIND)
         solve_lib.qpgpu_solve_batched_dual.argtypes = [ctypes.POINTER(qpgpu.ProblemDesc)] + [ctypes.c_void_p] * 13
         solve_lib.qpgpu_solve_batched_dual.restype = ctypes.c_int
+        solve_lib.qpgpu_vjp.argtypes = [ctypes.POINTER(qpgpu.ProblemDesc)] + [ctypes.c_void_p] * 14
+        solve_lib.qpgpu_vjp_ws.argtypes = ([ctypes.POINTER(qpgpu.ProblemDesc)] + [ctypes.c_void_p] * 13
+                                           + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p])
+        solve_lib.qpgpu_vjp.restype = solve_lib.qpgpu_vjp_ws.restype = ctypes.c_int
     lines = []
     for name in args.shapes.split(","):
         n, p, m, B = SHAPES[name]
@@ -88,6 +103,8 @@ def main():
                 rows = db.x.shape[0]
                 db.u = torch.zeros((rows, p + m), dtype=torch.float64, device=dev)
                 db.gx = torch.randn((rows, n), dtype=torch.float64, device=dev)
+                db.gu = torch.randn((rows, p + m), dtype=torch.float64, device=dev)
+                db.gf = torch.randn(B, dtype=torch.float64, device=dev)
                 db.grads = {k: torch.empty((rows, db._vjp_elems(k)), dtype=torch.float64, device=dev)
                             for k in db._VJP_OUTPUTS}
                 d = qpgpu.ProblemDesc(n, p, m, 0, B, 0, db.layout)
@@ -110,6 +127,21 @@ def main():
                 db = sets[q % R]
                 db.vjp(db.u, db.gx, outs=db.grads, stream=s, workspace=spaces.get(slots_now[0]))
 
+            def vjp_full(q):
+                db = sets[q % R]
+                db.vjp(db.u, db.gx, outs=db.grads, stream=s, workspace=spaces.get(slots_now[0]), gu=db.gu, gf=db.gf)
+
+            def vjp_parent(q):  # the x-only entry of the parent's build, on the same device arrays
+                db = sets[q % R]
+                a = ([ctypes.byref(db.solve_args[0])] + [vp(t) for t in (db.G, db.CE, db.CI, db.x, db.u, db.status, db.gx)]
+                     + [vp(db.grads[k]) for k in db._VJP_OUTPUTS])
+                if spaces:
+                    ws = spaces[slots_now[0]]
+                    rc = solve_lib.qpgpu_vjp_ws(*a, vp(ws), ws.numel(), ctypes.c_void_p(s.cuda_stream))
+                else:
+                    rc = solve_lib.qpgpu_vjp(*a, ctypes.c_void_p(s.cuda_stream))
+                assert rc == 0, rc
+
             def timed(fn, q):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(s)
@@ -127,12 +159,47 @@ def main():
                 solve(q)
                 q += 1
                 torch.cuda.synchronize()
+            st = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+            if args.full:
+                kinds = {"vjp_full": vjp_full, "vjp": vjp}
+                if args.parent_lib:
+                    kinds["vjp_parent"] = vjp_parent
+                for k in range(2):  # untimed
+                    for fn in kinds.values():
+                        q += 1
+                        fn(q)
+                torch.cuda.synchronize()
+                ms = {k: [] for k in kinds}
+                order = list(kinds.items())
+                for k in range(args.reps):
+                    for name_, fn in order:  # every launch on the next input set: cold inputs for each kind
+                        q += 1
+                        ms[name_].append(timed(fn, q))
+                    order = order[1:] + order[:1]  # and no kind always behind the same other
+                vjp_full(0)
+                torch.cuda.synchronize()
+                g = sets[0].vjp_rows(sets[0].grads)
+                med = {k: float(np.median(v)) for k, v in ms.items()}
+                rec = {"mode": "full", "shape": name, "n": n, "p": p, "m": m, "batch": B, "layout": layout,
+                       "input_sets": R, "reps": args.reps, "slots": slot_counts[0] or None,
+                       "vjp_full_kernel": qpgpu.kernel_name_vjp_full(n, p, m),
+                       "vjp_kernel": qpgpu.kernel_name_vjp_ws(n, p, m), "parent_lib": args.parent_lib,
+                       **{k + "_ms": st(v) for k, v in ms.items()},
+                       "full_over_vjp": med["vjp_full"] / med["vjp"],
+                       "vjp_over_parent": med["vjp"] / med["vjp_parent"] if "vjp_parent" in med else None,
+                       "extra_reads_per_qp": p + m + 1,
+                       "all_finite": bool(all(np.all(np.isfinite(v)) for v in g.values())),
+                       **{k + "_raw_ms": [round(v, 4) for v in vs] for k, vs in ms.items()}}
+                lines.append(json.dumps(rec))
+                print(lines[-1], flush=True)
+                del sets, base, spaces
+                torch.cuda.empty_cache()
+                continue
             ms = {"vjp": [], "solve": []}
             for k in range(args.reps):
                 q += 1
                 ms["vjp"].append(timed(vjp, q))
                 ms["solve"].append(timed(solve, q))
-            st = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
             by_slots = {str(slot_counts[0]): st(ms["vjp"])} if spaces else None
             for k in slot_counts[1:]:
                 slots_now[0] = k
