@@ -602,6 +602,78 @@ int qpgpu_vjp_box_full(const qpgpu_problem_desc* d,
  * n > 256 or n <= 0. */
 const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t p, int32_t m);
 
+/* ---- forward-mode sensitivities: how x*, the multipliers and the optimal value move ----------------
+ * qpgpu_jvp evaluates, on the device, the Jacobian-vector product of every QP of a batch: given a
+ * tangent (tG, tg0, tCE, tce0, tCI, tci0) of the data, the tangents tx of x*, tu of the multipliers
+ * and tf of the optimal value.  With A, lam and b as at qpgpu_vjp, G x + g0 = A lam and A^T x + b = 0;
+ * differentiating,
+ *     G tx - A tlam = h,   A^T tx = k,      h = tA lam - tG x - tg0,   k = -(tA^T x + tb),
+ * and with w = L^-1 h:  (M^T M) tlam = k - M^T w,  tx = L^-T (w + M tlam).  By the envelope theorem
+ *     tf = 1/2 x^T tG x + tg0^T x + lam^T k.
+ * A multiplier outside W is locally the constant 0 (the one-sided choice of qpgpu_vjp): its tu is
+ * +0.0, and the column of tCI and the entry of tci0 of an inequality outside W never enter the
+ * arithmetic: they may hold anything, NaN included, without changing a bit of any output.  tG is
+ * read as stored, row by row: a symmetric tangent is assumed.
+ *
+ * Device pointers, enqueue only, no allocation, no workspace: a first call can be captured into a
+ * hipGraph.  G, CE, CI, x, u and status are laid out as qpgpu_vjp takes them, in either layout; every
+ * tangent has the layout and the per-QP size of the array it is the tangent of.  Each tangent may be
+ * NULL: a NULL tangent is a zero tangent, and the steps marked [given] below are then not executed.
+ * tx is n doubles per QP in the layout of x, tu p + m doubles per QP in the layout of u, tf one
+ * double per QP at tf[b] in either layout, like f.  Each output may be NULL: it is then neither
+ * computed nor written; all three NULL is QPGPU_SUCCESS and writes nothing.  Natural alignment and
+ * sub-ranges as at the top of this file; the call writes the requested outputs of its own QPs and
+ * nothing else (no TILED64 padding slot, no input).
+ *
+ * Shapes: n <= 64 with any p and any m (n*n, n*p and n*m below 2^31); n > 64 is
+ * QPGPU_ERR_UNSUPPORTED_SHAPE (a workspace form is not built).  d->max_iter is ignored; d->flags
+ * must be 0.  The argument rules and their order are qpgpu_vjp's, decided before any array is read,
+ * QPGPU_ERR_INVALID_ARGUMENT: non-zero flags; a NULL u with p + m > 0; with batch > 0 a NULL G or x, a
+ * NULL CE with p > 0, a NULL CI with m > 0.  The shape rule comes after these.  batch = 0 is
+ * QPGPU_SUCCESS.  status may be NULL: every QP is evaluated.  With status given, a QP whose status is
+ * not QPGPU_QP_OK gets +0.0 in every requested output.
+ *
+ * The definition, which the kernels reproduce bit for bit (tests/jvp_ref.py restates it).  No FMA,
+ * every product rounded before it is added or subtracted, IEEE division and sqrt, no branch on a
+ * pivot, every sum from +0.0 and ascending.  W, q, col(t), lam(t), chol, fsub and bsub are exactly
+ * as at qpgpu_vjp; tcol(t) is the tCE or tCI column at position t, tb(t) its tce0 or tci0 entry.  If
+ * q > n, every requested output element of the QP is NaN.
+ *   sG[i] = sum_j tG[i][j]*x[j]                                           [tG given; else +0.0]
+ *   h[i]  = +0.0;  for t ascending: h[i] = h[i] + tcol(t)[i]*lam(t)       [tCE / tCI given, per matrix]
+ *           h[i] = h[i] - sG[i]  [tG given];   h[i] = h[i] - tg0[i]  [tg0 given]
+ *   s     = sum_i tcol(t)[i]*x[i]  [given; else +0.0];   s = s + tb(t)  [tce0 / tci0 given];   k[t] = -s
+ *   L = chol(G);  w = fsub(L, h);  M[:,t] = fsub(L, col(t))
+ *   S[s][t] = sum_i M[i][s]*M[i][t] for s >= t,   rs[t] = sum_i M[i][t]*w[i]
+ *   r[t] = k[t] - rs[t];  R = chol(S);  dl = bsub(R, fsub(R, r))
+ *   y[i] = w[i], then for t ascending y[i] = y[i] + M[i][t]*dl[t];  tx = bsub(L, y)
+ *   tu[k] = dl[k] for k < p;  tu[p+j] = dl[t] for inequality j at position t of W;  +0.0 elsewhere
+ *   qq = sum_i x[i]*sG[i];  ll = sum_i tg0[i]*x[i]  [tg0 given; else +0.0];  kk = sum_t lam(t)*k[t]
+ *   tf = ((0.5*qq) + ll) + kk */
+int qpgpu_jvp(const qpgpu_problem_desc* d,
+              const double* G, const double* CE, const double* CI,
+              const double* x, const double* u, const int32_t* status,
+              const double* tG, const double* tg0, const double* tCE, const double* tce0,
+              const double* tCI, const double* tci0,
+              double* tx, double* tu, double* tf, void* stream);
+
+/* The same for bounds lo <= x <= hi, with u and tu in the layout of qpgpu_solve_batched_box_dual
+ * (p + 2n doubles per QP; d->m must be 2 * d->n: anything else is QPGPU_ERR_INVALID_ARGUMENT); thi and
+ * tlo are n doubles per QP in the layout of x.  col(t) is generated as in qpgpu_vjp_box; a bound's
+ * column has no tangent: its h-step and its s-sum are skipped;  tb(t) = thi[k] for the upper bound
+ * of k [thi given],  tb(t) = -tlo[k] (IEEE negation) for the lower bound of k [tlo given].  DEFINED
+ * as, and bit-equal to, qpgpu_jvp on BoxProblems.to_dense() with tCI = NULL and tci0 = [thi; -tlo]. */
+int qpgpu_jvp_box(const qpgpu_problem_desc* d,
+                  const double* G, const double* CE,
+                  const double* x, const double* u, const int32_t* status,
+                  const double* tG, const double* tg0, const double* tCE, const double* tce0,
+                  const double* thi, const double* tlo,
+                  double* tx, double* tu, double* tf, void* stream);
+
+/* Name of the kernel a qpgpu_jvp / qpgpu_jvp_box launch of this shape runs: a name containing "jvp",
+ * and "lane" (one QP per lane) for n <= 8, "group" (one QP per 16, 32 or 64 lanes) for
+ * 8 < n <= 64; "" for n > 64 or n <= 0. */
+const char* qpgpu_kernel_name_jvp(int32_t n, int32_t p, int32_t m);
+
 /* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -20,6 +20,7 @@
 #include "../../include/qpgpu.h"
 #include "qp_common.h"
 #include "qp_kkt.h"
+#include "qp_jvp.h"
 #include "qp_vjp.h"
 
 extern "C" int qpk_medium_max_n(void);
@@ -701,6 +702,60 @@ const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t p, int32_t m) {
   (void)m;
   const char* k = qpk_vjp_full_name(n);
   if (!k) k = qpk_vjp_ws_full_name(n);
+  return k ? k : "";
+}
+
+// ---- forward-mode sensitivities (include/qpgpu.h; kernels: qp_jvp.hip) ---------------
+// The rules are vjp_rules' without gx, in the same order, decided before any array is read; no
+// workspace, one kernel, so the first call for a shape can be captured.
+static int jvp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                   const double* CI, const double* x, const double* u, const int32_t* status,
+                   const double* tG, const double* tg0, const double* tCE, const double* tce0,
+                   const double* tCI, const double* tci0, const double* thi, const double* tlo, double* tx,
+                   double* tu, double* tf, void* stream) {
+  if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
+    return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->flags != 0) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (box && (int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
+  if ((int64_t)d->p + d->m > 0 && !u) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (d->batch > 0) {
+    if (!G || !x) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (d->p > 0 && !CE) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (!box && d->m > 0 && !CI) return QPGPU_ERR_INVALID_ARGUMENT;
+  }
+  // n <= 64: L, M and S of a QP fit on chip
+  if (!qpk_jvp_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  if (d->batch == 0 || (!tx && !tu && !tf)) return QPGPU_SUCCESS;
+  const qpk::JvpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status,
+                          tG, tg0, tCE, tce0, box ? nullptr : tCI, box ? nullptr : tci0, box ? thi : nullptr,
+                          box ? tlo : nullptr, tx, tu, tf};
+  const hipError_t e = qpk_launch_jvp(&a, d->layout == QPGPU_LAYOUT_TILED64, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_jvp(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* CI,
+              const double* x, const double* u, const int32_t* status, const double* tG, const double* tg0,
+              const double* tCE, const double* tce0, const double* tCI, const double* tci0, double* tx,
+              double* tu, double* tf, void* stream) {
+  return jvp_run(d, false, G, CE, CI, x, u, status, tG, tg0, tCE, tce0, tCI, tci0, nullptr, nullptr, tx, tu, tf,
+                 stream);
+}
+
+int qpgpu_jvp_box(const qpgpu_problem_desc* d, const double* G, const double* CE, const double* x,
+                  const double* u, const int32_t* status, const double* tG, const double* tg0,
+                  const double* tCE, const double* tce0, const double* thi, const double* tlo, double* tx,
+                  double* tu, double* tf, void* stream) {
+  return jvp_run(d, true, G, CE, nullptr, x, u, status, tG, tg0, tCE, tce0, nullptr, nullptr, thi, tlo, tx, tu, tf,
+                 stream);
+}
+
+const char* qpgpu_kernel_name_jvp(int32_t n, int32_t p, int32_t m) {
+  (void)p;
+  (void)m;
+  const char* k = qpk_jvp_name(n);
   return k ? k : "";
 }
 

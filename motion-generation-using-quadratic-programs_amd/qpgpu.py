@@ -83,6 +83,9 @@ EXPORTED_SYMBOLS = (
     "qpgpu_vjp_full",
     "qpgpu_vjp_box_full",
     "qpgpu_kernel_name_vjp_full",
+    "qpgpu_jvp",
+    "qpgpu_jvp_box",
+    "qpgpu_kernel_name_jvp",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -161,6 +164,12 @@ def _load():
     lib.qpgpu_vjp_box_full.restype = ctypes.c_int
     lib.qpgpu_kernel_name_vjp_full.argtypes = [ctypes.c_int32] * 3
     lib.qpgpu_kernel_name_vjp_full.restype = ctypes.c_char_p
+    lib.qpgpu_jvp.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 16
+    lib.qpgpu_jvp.restype = ctypes.c_int
+    lib.qpgpu_jvp_box.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 15
+    lib.qpgpu_jvp_box.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_jvp.argtypes = [ctypes.c_int32] * 3
+    lib.qpgpu_kernel_name_jvp.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -255,6 +264,15 @@ def kernel_name_vjp_full(n: int, p: int = 0, m: int = 0) -> str:
     """The kernel a qpgpu_vjp_full / qpgpu_vjp_box_full launch of this shape runs: a name with "full"
     in it, and "lane" for n <= 8, "group" for 8 < n <= 64, "ws" for 64 < n <= 256; "" beyond."""
     return LIB.qpgpu_kernel_name_vjp_full(n, p, m).decode()
+
+
+def kernel_name_jvp(n: int, p: int = 0, m: int = 0) -> str:
+    """The kernel a qpgpu_jvp / qpgpu_jvp_box launch of this shape runs: a name with "jvp", and "lane"
+    for n <= 8, "group" for 8 < n <= 64; "" for n > 64 or n <= 0."""
+    return LIB.qpgpu_kernel_name_jvp(n, p, m).decode()
+
+
+JVP_OUTPUTS = ("tx", "tu", "tf")
 
 
 def vjp_workspace_bytes(n: int, p: int, m: int, slots: int) -> int:
@@ -577,7 +595,8 @@ class _DeviceBatchBase:
     with multipliers, KKT check)."""
 
     _INPUTS = ()
-    _ENTRY = _ENTRY_DUAL = _ENTRY_KKT = _ENTRY_VJP = None
+    _ENTRY = _ENTRY_DUAL = _ENTRY_KKT = _ENTRY_VJP = _ENTRY_JVP = None
+    _JVP_TANGENTS = ()  # the inputs the forward-mode entry takes a tangent of, in its C entry's order
     _VJP_INPUTS = ()   # the inputs the backward step reads, in its C entry's order
     _VJP_OUTPUTS = ()  # its six gradients, in its C entry's order
 
@@ -721,6 +740,56 @@ class _DeviceBatchBase:
                 res[k] = h[:self.batch * self._vjp_elems(k)].reshape((self.batch,) + shapes[k])
         return res
 
+    def jvp(self, u, tangents, outs=None, status=True, stream=None, x=None):
+        """Enqueue the forward-mode sensitivities (qpgpu_jvp / qpgpu_jvp_box, include/qpgpu.h) of this
+        batch's resident inputs at (x, u) on `stream` (default current): no host round trip, so it
+        can follow a dual solve on the same stream.  u, status and x as vjp() takes them.  tangents: a
+        dict from input name (G, g0, CE, ce0 and CI, ci0 or hi, lo) to a float64 device tensor in this
+        batch's layout, shaped like that input; a missing name (or None) is passed as NULL, a zero
+        tangent.  outs: None computes tx, tu and tf into new tensors; otherwise a dict from output
+        name to the tensor to write, or True to allocate it: an output that is not named is passed
+        as NULL and not computed.  Returns the dict of the tensors written: tx (rows, n) and tu
+        (rows, p + m) in this batch's layout, tf (batch,) (jvp_rows() decodes host copies)."""
+        import torch
+
+        x = self.x if x is None else x
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        for k in tangents:
+            if k not in self._JVP_TANGENTS:
+                raise ValueError(f"{k!r} is no tangent of {self._ENTRY_JVP}: {self._JVP_TANGENTS}")
+        rows = x.numel() // self.n
+        shapes = {"tx": (rows, self.n), "tu": (rows, self.p + self.m), "tf": (self.batch,)}
+        outs = dict.fromkeys(JVP_OUTPUTS, True) if outs is None else dict(outs)
+        for k in outs:
+            if k not in JVP_OUTPUTS:
+                raise ValueError(f"{k!r} is no output of {self._ENTRY_JVP}: {JVP_OUTPUTS}")
+            if outs[k] is True:
+                outs[k] = torch.empty(shapes[k], dtype=torch.float64, device=x.device)
+        st = self.status if status is True else (None if status is None or status is False else status)
+        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        tensors = ([getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st] + [tangents.get(k) for k in self._JVP_TANGENTS]
+                   + [outs.get(k) for k in JVP_OUTPUTS])
+        _check(getattr(LIB, self._ENTRY_JVP)(ctypes.byref(d), *[vp(t) for t in tensors],
+                                             ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_JVP)
+        return outs
+
+    def jvp_rows(self, outs):
+        """A jvp() result as numpy arrays: tx (batch, n), tu (batch, p + m), tf (batch,), whatever the
+        layout."""
+        shapes = {"tx": (self.n,), "tu": (self.p + self.m,)}
+        res = {}
+        for k, t in outs.items():
+            h = t.cpu().numpy().reshape(-1)
+            if k == "tf":
+                res[k] = h[:self.batch].copy()
+            elif self.layout == LAYOUT_TILED64:
+                res[k] = from_tiled64(h, self.batch, shapes[k])
+            else:
+                res[k] = h[:self.batch * shapes[k][0]].reshape((self.batch,) + shapes[k])
+        return res
+
     def kkt_rows(self, r):
         """A kkt_residuals() result as numpy (batch, 8), whatever the layout."""
         rh = r.cpu().numpy()
@@ -745,6 +814,8 @@ class DeviceBatch(_DeviceBatchBase):
     _ENTRY_VJP = "qpgpu_vjp"
     _VJP_INPUTS = ("G", "CE", "CI")
     _VJP_OUTPUTS = ("dG", "dg0", "dCE", "dce0", "dCI", "dci0")
+    _ENTRY_JVP = "qpgpu_jvp"
+    _JVP_TANGENTS = ("G", "g0", "CE", "ce0", "CI", "ci0")
 
     def __init__(self, pr: Problems, device, with_iters: bool = True, layout=None):
         super().__init__(pr, device, with_iters, layout)
@@ -787,6 +858,8 @@ class DeviceBoxBatch(_DeviceBatchBase):
     _ENTRY_VJP = "qpgpu_vjp_box"
     _VJP_INPUTS = ("G", "CE")
     _VJP_OUTPUTS = ("dG", "dg0", "dCE", "dce0", "dhi", "dlo")
+    _ENTRY_JVP = "qpgpu_jvp_box"
+    _JVP_TANGENTS = ("G", "g0", "CE", "ce0", "hi", "lo")
 
     def __init__(self, bp: BoxProblems, device, with_iters: bool = True, layout=None):
         super().__init__(bp, device, with_iters, layout)
@@ -977,6 +1050,85 @@ def vjp(pr, x, u, gx, status=None, layout=None, device="cuda:0", outs=None, slot
                  gu=gud, gf=gfd)
     torch.cuda.synchronize(xd.device)
     return db.vjp_rows(res)
+
+
+def jvp(pr, x, u, tangents, status=None, layout=None, device="cuda:0", outs=None):
+    """The forward-mode sensitivities of every QP of `pr` (Problems: qpgpu_jvp; BoxProblems:
+    qpgpu_jvp_box) at the primal-dual pair (x, u), computed on the GPU: a dict of float64 arrays tx
+    (B, n), tu (B, p + m) and tf (B,) (include/qpgpu.h).  tangents: a dict from input name (G, g0, CE,
+    ce0 and CI, ci0, or hi, lo for bounds) to an array shaped like that input; a missing name (or None)
+    is a NULL tangent.  x is (B, n), u is (B, p + m) in QP-major order (may be None when
+    p + m == 0); with `status` (B int32) a QP that is not QP_OK gets +0.0 everywhere.  outs: the names
+    to compute (default all three).  layout="tiled64" runs the TILED64 form (converted here on the
+    host)."""
+    import torch
+
+    db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
+    B, E = pr.batch, pr.p + pr.m
+    conv = to_tiled64 if db.layout == LAYOUT_TILED64 else (lambda a: a)
+    up = lambda a, cols: torch.from_numpy(np.array(
+        conv(np.asarray(a, dtype=np.float64).reshape(B, cols)), dtype=np.float64, order="C")).to(device)
+    xd = up(x, pr.n)
+    ud = up(u, E) if E > 0 else None
+    sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
+    td = {k: up(t, np.asarray(t).size // B) for k, t in tangents.items() if t is not None and np.asarray(t).size}
+    res = db.jvp(ud, td, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd)
+    torch.cuda.synchronize(xd.device)
+    return db.jvp_rows(res)
+
+
+def _qp_jvp(box, G, g0, CE, ce0, c5, c6, tangents):
+    import torch
+
+    B, n, p = G.shape[0], G.shape[-1], CE.shape[-1]
+    m = 2 * n if box else c5.shape[-1]
+    names = ("G", "g0", "CE", "ce0") + (("hi", "lo") if box else ("CI", "ci0"))
+    for t in (G, g0, CE, ce0, c5, c6) + tuple(t for t in tangents.values() if t is not None):
+        if t.dtype != torch.float64 or not t.is_cuda:
+            raise ValueError("qp_jvp takes float64 tensors on the GPU")
+    for k in tangents:
+        if k not in names:
+            raise ValueError(f"{k!r} is no input of the QP: {names}")
+    ins = [t.detach().contiguous() for t in (G, g0, CE, ce0, c5, c6)]
+    tan = [None if tangents.get(k) is None else tangents[k].detach().contiguous() for k in names]
+    for k, a, t in zip(names, ins, tan):
+        if t is not None and t.shape != a.shape:
+            raise ValueError(f"the tangent of {k} has shape {tuple(t.shape)}, not {tuple(a.shape)}")
+    dev = G.device
+    x = torch.zeros((B, n), dtype=torch.float64, device=dev)
+    f = torch.empty(B, dtype=torch.float64, device=dev)
+    st = torch.empty(B, dtype=torch.int32, device=dev)
+    u = torch.zeros((B, p + m), dtype=torch.float64, device=dev)
+    tx = torch.empty((B, n), dtype=torch.float64, device=dev)
+    tu = torch.empty((B, p + m), dtype=torch.float64, device=dev)
+    tf = torch.empty(B, dtype=torch.float64, device=dev)
+    d = ProblemDesc(n, p, m, 0, B, 0, LAYOUT_QP_MAJOR)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    entry = "qpgpu_solve_batched_box_dual" if box else "qpgpu_solve_batched_dual"
+    _check(getattr(LIB, entry)(ctypes.byref(d), *[vp(t) for t in ins], vp(x), vp(f), vp(st), None, vp(u), None,
+                               stream), entry)
+    entry = "qpgpu_jvp_box" if box else "qpgpu_jvp"
+    data = (vp(ins[0]), vp(ins[2])) + (() if box else (vp(ins[4]),))
+    _check(getattr(LIB, entry)(ctypes.byref(d), *data, vp(x), vp(u), vp(st), *[vp(t) for t in tan], vp(tx), vp(tu),
+                               vp(tf), stream), entry)
+    return x, u, f, st, tx, tu, tf
+
+
+def qp_jvp(G, g0, CE, ce0, CI, ci0, tangents):
+    """The batched QP and its forward-mode sensitivities in one call: (x, u, f, status, tx, tu, tf) for
+    float64 device tensors shaped as qp_layer takes them and `tangents`, a dict from input name (G, g0,
+    CE, ce0, CI, ci0) to a tensor shaped like that input (a missing name: a zero tangent).  A dual
+    solve (qpgpu_solve_batched_dual), then qpgpu_jvp, on the current stream with no host round trip.
+    tx (B, n), tu (B, p + m) and tf (B,) are +0.0 for a QP whose status is not QP_OK.  Not hooked into
+    torch.autograd.forward_ad."""
+    return _qp_jvp(False, G, g0, CE, ce0, CI, ci0, tangents)
+
+
+def qp_jvp_box(G, g0, CE, ce0, hi, lo, tangents):
+    """qp_jvp for bounds lo <= x <= hi (tangent names G, g0, CE, ce0, hi, lo): u and tu are
+    (B, p + 2n), equalities, upper bounds, lower bounds (qpgpu_solve_batched_box_dual, then qpgpu_jvp_box)."""
+    return _qp_jvp(True, G, g0, CE, ce0, hi, lo, tangents)
 
 
 @functools.lru_cache(maxsize=None)
