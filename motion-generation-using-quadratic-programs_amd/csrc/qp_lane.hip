@@ -30,6 +30,7 @@
 // sqrt(a^2 + b^2) for operands well inside the exponent range — within north_star's 1e-10
 // relative of the reference instead of bit-identical.
 #include <type_traits>
+#include <utility>
 
 #include "qp_common.h"
 
@@ -140,6 +141,25 @@ constexpr int kStage = 5120;  // staging buffer, doubles (40 KiB: 4 waves per CU
 // j+1's loads are issued (and fenced from the scheduler) before row j is consumed, so one memory
 // latency covers two rows instead of the scheduler's one-load-at-a-time minimum-pressure order.
 constexpr int kScanDepth = 2;
+// The staging buffer as the LDS-DMA sees it.  The kernels cast their __shared__ array to LdsD
+// where it is declared (a constant the compiler folds) and lane_body keeps that pointer for the
+// copies' destinations: a generic pointer cast to address space 3 at each copy is a run-time
+// generic -> local conversion, which the compiler guards with a null test ahead of every M0 write.
+using LdsD = __attribute__((address_space(3))) double;
+using LdsC = __attribute__((address_space(3))) char;
+using LdsV = __attribute__((address_space(3))) void;
+using GlobalV = __attribute__((address_space(1))) void;
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in that order: the LDS-DMA
+// builtin's offset is an immediate of the instruction, so a chunk or piece index that reaches it
+// has to be a constant expression (a fully unrolled loop's counter is not one).
+template <int... K, class F>
+__device__ __forceinline__ void for_seq_impl(std::integer_sequence<int, K...>, F&& f) {
+  (f(std::integral_constant<int, K>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void for_seq(F&& f) {
+  for_seq_impl(std::make_integer_sequence<int, N>{}, f);
+}
 // Choices of the staging that measurements settled (the other sides: DESIGN §5.15):
 //   * p = 0 (no equality phase): the first scan loads the CI rows, no DMA copies them into LDS.
 //     Measured on C2 (profiles/r03_s6): 83.6 us with the DMA at the end of the setup, 72.9
@@ -194,7 +214,8 @@ constexpr int kScanDepth = 2;
 // branches.  The arithmetic is the same operations in the same order.
 template <int NM, int MM, int T, bool EXACT, int PX, bool SAFE, bool DUAL = false, bool BOX = false,
           bool FULL = false>
-__device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
+__device__ __forceinline__ bool lane_body(const QpArgs& a, LdsD* lds) {
+  double* const sbuf = (double*)lds;  // the LDS reads and the per-lane copies (LDS-DMA: lds)
   static_assert(MM <= 64, "bitmask bookkeeping holds m <= 64");
   static_assert(!BOX || (!kFast && MM == 2 * NM), "the box mode is the exact build's, m = 2n");
   static_assert(!FULL || (!kFast && !QPGPU_LANE_UNALIGNED && EXACT && PX >= 0 && !DUAL && !BOX),
@@ -230,20 +251,44 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // (b0*E*8 is a multiple of 512).  The host checks that for G, g0, CE and ce0 (kArgStage16) and
   // launches these kernels only then; otherwise it launches the QPGPU_LANE_UNALIGNED build, where
   // every wave copies per lane, 8 bytes at a time, in both layouts.  (Preprocessor, not
-  // `if constexpr`: the aligned build's text stays token for token what it was, and so its code.)
+  // `if constexpr`: the unaligned build stages G, g0, CE and ce0 by stage_all's per-lane copy
+  // alone and never reaches copy_span; its CI copy, dma_ci_part, is the aligned build's.)
 #if QPGPU_LANE_UNALIGNED
   const bool full = false;
 #else
   const bool full = FULL || (T == 64) || (valid == kQpw);
 #endif
-  auto copy_chunk = [&](const double* src, int nd, int off, int k) {  // doubles [k, k+128)
-    const int e = k + 2 * lane;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(e < nd ? src + e : src),
-                                     (__attribute__((address_space(3))) void*)(sbuf + off + k), 16, 0, 0);
+  // Chunk J (0..3) of the run of chunks that starts at double k0 of a span: doubles
+  // [k0 + 128 J, k0 + 128 J + 128).  J goes in the instruction's immediate offset, which the
+  // hardware adds to the global address and to the LDS address (M0 + offset + 16 * lane) alike:
+  // both strides are 1 KiB here, so the chunks of a run share one per-lane source address and one
+  // M0, and four chunks fit the 13-bit signed immediate.  The lanes past the span's end load from
+  // src instead: with the immediate that is the first piece of the span's own chunk J, which lies
+  // inside the span whenever chunk J of any run is issued.
+  auto copy_chunk = [&](auto J, const double* src, int nd, int off, int k0) {
+    constexpr int j = decltype(J)::value;
+    static_assert(j >= 0 && j * 1024 < 4096, "the chunk's offset is the instruction's immediate");
+    const int e = k0 + 2 * lane;
+    __builtin_amdgcn_global_load_lds((const GlobalV*)(e + j * 128 < nd ? src + e : src),
+                                     (LdsV*)(lds + off + k0), 16, j * 1024, 0);
   };
+  auto copy_run = [&](const double* src, int nd, int off, int k0) {  // the chunks of [k0, k0 + 512)
+    copy_chunk(std::integral_constant<int, 0>{}, src, nd, off, k0);
+    if (k0 + 128 < nd) copy_chunk(std::integral_constant<int, 1>{}, src, nd, off, k0);
+    if (k0 + 256 < nd) copy_chunk(std::integral_constant<int, 2>{}, src, nd, off, k0);
+    if (k0 + 384 < nd) copy_chunk(std::integral_constant<int, 3>{}, src, nd, off, k0);
+  };
+  // The full-wave kernels unroll the span into its runs (straight-line code, every test folded).
+  // The others keep the loop over single chunks: unrolled or run-wise spans grew their static size
+  // and the scratch of some N = 8 instantiations (profiles/lane_dma/isa_census.txt).
   auto copy_span = [&](const double* src, int nd, int off) {  // nd even, full waves only
+    if constexpr (FULL) {
+#pragma unroll
+      for (int k0 = 0; k0 < nd; k0 += 512) copy_run(src, nd, off, k0);
+    } else {
 #pragma unroll 4
-    for (int k = 0; k < nd; k += 128) copy_chunk(src, nd, off, k);
+      for (int k = 0; k < nd; k += 128) copy_chunk(std::integral_constant<int, 0>{}, src, nd, off, k);
+    }
   };
   // whole tile of X (E doubles per QP) -> sbuf[off...]
 #if QPGPU_LANE_UNALIGNED
@@ -337,16 +382,20 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
   // part by part between compute steps (part `part` of `parts`): all 35 pieces at once stall
   // the wave's issue until HBM has delivered most of them (the CU's memory queues fill), which
   // serialised the whole CI transfer with the setup (+25k cycles per wave, profiles/r03_s4).
+  // The piece index goes in the instruction's immediate offset (16 k bytes: the global stride),
+  // which the hardware adds to the LDS address as well, where the stride is 1 KiB: piece k's LDS
+  // base is k * (1024 - 16).  One per-lane source address serves every piece of every part.
   constexpr int kCiPieces = kCiRows * MM / 2;
+  static_assert(kCiPieces * 16 <= 4096, "the piece's offset is the instruction's immediate");
   auto dma_ci_part = [&](int part, int parts) {
     const int per = (kCiPieces + parts - 1) / parts;
     const double* src = a.CI + (live ? b : b0) * (int64_t)(NM * MM);
-#pragma unroll
-    for (int k = 0; k < kCiPieces; k++)
+    for_seq<kCiPieces>([&](auto K) {
+      constexpr int k = decltype(K)::value;
       if (k >= part * per && k < (part + 1) * per)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * k),
-                                         (__attribute__((address_space(3))) void*)(sbuf + k * 2 * kQpw),
-                                         16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const GlobalV*)src, (LdsV*)((LdsC*)lds + k * (kQpw * 16 - 16)), 16,
+                                         16 * k, 0);
+    });
   };
   lstamp(a, 0);
   // BOX: b = [hi; -lo] at the positions above, loaded first so that the setup hides the latency
@@ -402,7 +451,8 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     const int npB = n * p;
     const int offcB = (kQpw * npB + 127) / 128 * 128;
     const bool stageB = p > 0 && offcB + kQpw * p <= STAGE;
-    auto round_b = [&](int part, int parts) {
+    auto round_b = [&](int part) {  // part `part` of NM
+      constexpr int parts = NM;
       if (!stageB) return;
       if (!full) {
         if (part == 0) {
@@ -411,15 +461,34 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
         }
         return;
       }
-      const int nce = (kQpw * npB + 127) / 128, tot = nce + (kQpw * p + 127) / 128;
-      const int per = (tot + parts - 1) / parts;
       const double* ce = a.CE + b0 * (int64_t)npB;
       const double* c0 = a.ce0 + b0 * (int64_t)p;
-      for (int c = part * per; c < min(tot, (part + 1) * per); c++) {
-        if (c < nce)
-          copy_chunk(ce, kQpw * npB, 0, c * 128);
-        else
-          copy_chunk(c0, kQpw * p, offcB, (c - nce) * 128);
+      if constexpr (EXACT && PX > 0) {
+        // the shape is compile-time: the chunks of a part that lie in one array are runs of up to
+        // four on one source address and one M0 (copy_chunk), in the same ascending order
+        constexpr int nce = (kQpw * NM * PX + 127) / 128, tot = nce + (kQpw * PX + 127) / 128;
+        constexpr int per = (tot + parts - 1) / parts;
+        for_seq<tot>([&](auto C) {
+          constexpr int c = decltype(C)::value;
+          constexpr int arr = c < nce ? 0 : nce;                         // the array's first chunk
+          constexpr int run = c - c % per > arr ? c - c % per : arr;     // the part's, within the array
+          constexpr int j = (c - run) % 4, k0 = (c - j - arr) * 128;     // chunk j of the run at k0
+          if (c >= part * per && c < (part + 1) * per) {
+            if constexpr (c < nce)
+              copy_chunk(std::integral_constant<int, j>{}, ce, kQpw * NM * PX, 0, k0);
+            else
+              copy_chunk(std::integral_constant<int, j>{}, c0, kQpw * PX, nce * 128, k0);
+          }
+        });
+      } else {
+        const int nce = (kQpw * npB + 127) / 128, tot = nce + (kQpw * p + 127) / 128;
+        const int per = (tot + parts - 1) / parts;
+        for (int c = part * per; c < min(tot, (part + 1) * per); c++) {
+          if (c < nce)
+            copy_chunk(std::integral_constant<int, 0>{}, ce, kQpw * npB, 0, c * 128);
+          else
+            copy_chunk(std::integral_constant<int, 0>{}, c0, kQpw * p, offcB, (c - nce) * 128);
+        }
       }
     };
 #if QPGPU_LANE_UNIT
@@ -430,7 +499,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     // within the spread on (7, 0, 14).
 #pragma unroll
     for (int i = 0; i < NM; i++) {
-      round_b(i, NM);
+      round_b(i);
       if (i < n) c1 += 1.0;
     }
 #else
@@ -440,7 +509,7 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, double* sbuf) {
     // cholesky_decomposition (@.text+0x2df0): row-wise, descending-k sums, upper mirrored
 #pragma unroll
     for (int i = 0; i < NM; i++) {
-      round_b(i, NM);  // every lane (the copy is per wave)
+      round_b(i);  // every lane (the copy is per wave)
       if (i < n && chol_ok) {
         double sum = Gr[i][i];
 #pragma unroll
@@ -1581,12 +1650,12 @@ template <int NM, int MM, int T, bool EXACT, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
   __shared__ double sbuf[kStage];
   if constexpr (kFast) {
-    if (!lane_body<NM, MM, T, EXACT, PX, false>(a, sbuf)) {
+    if (!lane_body<NM, MM, T, EXACT, PX, false>(a, (LdsD*)sbuf)) {
       __syncthreads();  // the fast attempt's LDS traffic is over
-      lane_body<NM, MM, T, EXACT, PX, true>(a, sbuf);
+      lane_body<NM, MM, T, EXACT, PX, true>(a, (LdsD*)sbuf);
     }
   } else {
-    lane_body<NM, MM, T, EXACT, PX, true>(a, sbuf);
+    lane_body<NM, MM, T, EXACT, PX, true>(a, (LdsD*)sbuf);
   }
 }
 
@@ -1628,7 +1697,7 @@ extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m) {
 template <int NM, int MM, int T, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_full_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
-  lane_body<NM, MM, T, true, PX, true, false, false, true>(a, sbuf);
+  lane_body<NM, MM, T, true, PX, true, false, false, true>(a, (LdsD*)sbuf);
 }
 // Does the full-wave kernel exist for this instantiation, and has the host established what it
 // assumes of the launch (apart from the whole waves, which launch_full_then_rest provides)?
@@ -1680,21 +1749,21 @@ static void launch_full_then_rest(const QpArgs& a, Full&& full, Rest&& rest) {
 template <int NM, int MM, int T>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_dual_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
-  lane_body<NM, MM, T, false, -1, true, true>(a, sbuf);
+  lane_body<NM, MM, T, false, -1, true, true>(a, (LdsD*)sbuf);
 }
 // qpgpu_solve_batched_box: bounds instead of CI.  Kernels of their own: the compile-time p = 0
 // form of the exact shape (EXACT, PX = 0) and the run-time-shape form (any p, n <= NM).
 template <int NM, int MM, int T, bool EXACT, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
-  lane_body<NM, MM, T, EXACT, PX, true, false, true>(a, sbuf);
+  lane_body<NM, MM, T, EXACT, PX, true, false, true>(a, (LdsD*)sbuf);
 }
 // qpgpu_solve_batched_box_dual: the two box forms with the multipliers carried and returned.
 // Kernels of their own again, so the box and dual kernels above are the same code as without them.
 template <int NM, int MM, int T, bool EXACT, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_dual_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
-  lane_body<NM, MM, T, EXACT, PX, true, true, true>(a, sbuf);
+  lane_body<NM, MM, T, EXACT, PX, true, true, true>(a, (LdsD*)sbuf);
 }
 #endif
 template <int NM, int MM, int T>
