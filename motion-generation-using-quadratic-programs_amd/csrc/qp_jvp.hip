@@ -29,13 +29,9 @@
 //
 // A QP masked by its status stores +0.0, one with more working columns than variables NaN, in every
 // requested output.  The box entry generates the columns of CI = [-I, +I] as qp_vjp.hip does; a
-// bound's column has no tangent, and tb is thi[k] or -tlo[k].  The helpers below are copies of
-// qp_vjp.hip's, whose text and register allocation stay as they are.
-#include <mutex>
-#include <set>
-#include <utility>
-
-#include "qp_common.h"
+// bound's column has no tangent, and tb is thi[k] or -tlo[k].  The substitutions, the group's
+// factorisation and the launch are qp_dense.h's, shared with qp_vjp.hip.
+#include "qp_dense.h"
 #include "qp_jvp.h"
 
 namespace qpk {
@@ -56,30 +52,7 @@ __device__ __forceinline__ void fill(const JvpArgs& g, int64_t b, double fv, int
   if (g.tf && first == 0) g.tf[b] = fv;
 }
 
-// element i of column j of CI = [-I, +I] (n x 2n)
-__device__ __forceinline__ double box_entry(int i, int j, int n) {
-  return j < n ? (i == j ? -1.0 : -0.0) : (i == j - n ? 1.0 : 0.0);
-}
-
-constexpr int tri(int i, int k) { return i * (i + 1) / 2 + k; }
-
 // ---- one QP per lane ----------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void lane_fsub(const double (&L)[N * (N + 1) / 2], double (&v)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double s = v[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s = s - L[tri(i, k)] * v[k];
-    v[i] = s / L[tri(i, i)];
-  }
-}
-
-#define MS(i, t) Ms[((i) * N + (t)) * 64 + lane]
-#define SS(s, t) Ss[tri((s), (t)) * 64 + lane]
-#define CS(t) Cs[(t) * 64 + lane]
-#define WS(t) Ws[(t) * 64 + lane]
-
 template <int T, int N, bool BOX>
 __global__ void __launch_bounds__(64) jvp_lane_kernel(JvpArgs g) {
   constexpr int NT = N * (N + 1) / 2;
@@ -260,17 +233,7 @@ __global__ void __launch_bounds__(64) jvp_lane_kernel(JvpArgs g) {
       SS(i, j) = r / d;
     }
   }
-  // dl = bsub(R, fsub(R, r)), in place
-  for (int i = 0; i < nq; i++) {
-    double s = CS(i);
-    for (int k = 0; k < i; k++) s = s - SS(i, k) * CS(k);
-    CS(i) = s / SS(i, i);
-  }
-  for (int i = nq - 1; i >= 0; i--) {
-    double s = CS(i);
-    for (int k = i + 1; k < nq; k++) s = s - SS(k, i) * CS(k);
-    CS(i) = s / SS(i, i);
-  }
+  lane_lds_solve(Ss, Cs, nq, lane);  // dl = bsub(R, fsub(R, r)), in place
   // y = w + M dl, tx = bsub(L, y)
   for (int t = 0; t < nq; t++) {
     const double dt = CS(t);
@@ -311,72 +274,8 @@ __global__ void __launch_bounds__(64) jvp_lane_kernel(JvpArgs g) {
     g.tf[b] = ((0.5 * qq) + ll) + kk;
   }
 }
-#undef MS
-#undef SS
-#undef CS
-#undef WS
 
 // ---- one QP per group of S lanes -----------------------------------------------------------------
-// doubles of LDS per group: three S x (S + 1) tiles, four vectors, the working list (S ints): the
-// backward step's footprint, so the same number of workgroups fits a CU (with three more vectors the
-// S = 32 kernel kept two workgroups per CU instead of three and took 2.24 ms instead of 1.57 ms on
-// C3).  sG and tg0, which the factorisations never read, live in the spare columns of
-// S's and L's tiles.
-template <int S>
-constexpr int group_doubles() {
-  return 3 * S * (S + 1) + 4 * S + S / 2;
-}
-
-// A = chol(A) in place on rows and columns [0, size) of a tile; lane sl owns row sl.  `bound` (>= size)
-// is the trip count, the same in every lane of the wave.
-template <int S>
-__device__ __forceinline__ void group_chol(double* A, int size, int bound, int sl, int base) {
-  constexpr int LD = S + 1;
-  for (int j = 0; j < bound; j++) {
-    double s = A[sl * LD + j];
-    for (int k = 0; k < j; k++) s = s - A[sl * LD + k] * A[j * LD + k];
-    const double sq = sqrt(s);
-    const double d = __shfl(sq, base + j, 64);  // lane j's: the pivot
-    const double val = sl == j ? sq : s / d;
-    if (j < size && sl >= j && sl < size) A[sl * LD + j] = val;
-    sg_sync();
-  }
-}
-
-// lane i's element of fsub(A, rhs) (rhs: lane i's element); z is the group's scratch vector
-template <int S>
-__device__ __forceinline__ double group_fsub(const double* A, int size, int bound, int sl, double rhs, double* z) {
-  constexpr int LD = S + 1;
-  double out = 0.0;
-  for (int i = 0; i < bound; i++) {
-    if (sl == i && i < size) {
-      double s = rhs;
-      for (int k = 0; k < i; k++) s = s - A[i * LD + k] * z[k];
-      out = s / A[i * LD + i];
-      z[i] = out;
-    }
-    sg_sync();
-  }
-  return out;
-}
-
-// the same for bsub(A, rhs): A^T z = rhs
-template <int S>
-__device__ __forceinline__ double group_bsub(const double* A, int size, int bound, int sl, double rhs, double* z) {
-  constexpr int LD = S + 1;
-  double out = 0.0;
-  for (int i = bound - 1; i >= 0; i--) {
-    if (sl == i && i < size) {
-      double s = rhs;
-      for (int k = i + 1; k < size; k++) s = s - A[k * LD + i] * z[k];
-      out = s / A[i * LD + i];
-      z[i] = out;
-    }
-    sg_sync();
-  }
-  return out;
-}
-
 template <int T, int S, bool BOX>
 __global__ void __launch_bounds__(64) jvp_group_kernel(JvpArgs g) {
   extern __shared__ double jvp_lds[];
@@ -576,22 +475,6 @@ static JvpKernel group_kernel_of(int n) {
                    : jvp_group_kernel<T, 64, BOX>;
 }
 
-// Dynamic LDS beyond 64 KiB is granted once per kernel and device; host threads may launch
-// concurrently (include/qpgpu.h), so the record is locked.
-static hipError_t grant_lds(const void* k, size_t bytes) {
-  static std::mutex mu;
-  static std::set<std::pair<const void*, int>> granted;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const std::pair<const void*, int> key(k, dev);
-  std::lock_guard<std::mutex> lk(mu);
-  if (granted.count(key)) return hipSuccess;
-  e = hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) granted.insert(key);
-  return e;
-}
-
 static hipError_t launch(const JvpArgs* a, int tiled, hipStream_t stream) {
   const int n = a->n;
   if (n < 1 || n > 64) return hipErrorInvalidValue;
@@ -603,38 +486,16 @@ static hipError_t launch(const JvpArgs* a, int tiled, hipStream_t stream) {
   else
     k = tiled ? (box ? group_kernel_of<64, true>(n) : group_kernel_of<64, false>(n))
               : (box ? group_kernel_of<1, true>(n) : group_kernel_of<1, false>(n));
-  const int S = n <= 16 ? 16 : n <= 32 ? 32 : 64;
-  const int64_t per_wg = lane ? 64 : 64 / S;  // QPs per workgroup (one wavefront)
-  size_t lds = 0;
-  if (!lane) {
-    const int per = S == 16 ? group_doubles<16>() : S == 32 ? group_doubles<32>() : group_doubles<64>();
-    lds = (size_t)per * (64 / S) * sizeof(double);
-    if (lds > 65536) {  // S = 64: beyond the default limit, inside the CU's 160 KiB
-      const hipError_t e = grant_lds(reinterpret_cast<const void*>(k), lds);
-      if (e != hipSuccess) return e;
-    }
-  }
-  JvpArgs c = *a;
-  const int64_t per = (int64_t)1 << 30;  // workgroups per launch: the grid stays inside 32 bits
-  for (int64_t w0 = 0; w0 * per_wg < a->batch; w0 += per) {
-    c.qp0 = w0 * per_wg;
-    const int64_t left = (a->batch - c.qp0 + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(k, dim3((unsigned)(left < per ? left : per)), dim3(64), lds, stream, c);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return launch_dense(k, a, stream);
 }
 
 }  // namespace jvp
 }  // namespace qpk
 
 extern "C" const char* qpk_jvp_name(int n) {
-  static const char* const lane[] = {"jvp_lane_n1", "jvp_lane_n2", "jvp_lane_n3", "jvp_lane_n4",
-                                     "jvp_lane_n5", "jvp_lane_n6", "jvp_lane_n7", "jvp_lane_n8"};
-  if (n < 1 || n > 64) return nullptr;
-  if (n <= 8) return lane[n - 1];
-  return n <= 16 ? "jvp_group_s16" : n <= 32 ? "jvp_group_s32" : "jvp_group_s64";
+  static const char* const names[] = {"jvp_lane_n1", "jvp_lane_n2", "jvp_lane_n3",   "jvp_lane_n4",   "jvp_lane_n5",  "jvp_lane_n6",
+                                      "jvp_lane_n7", "jvp_lane_n8", "jvp_group_s16", "jvp_group_s32", "jvp_group_s64"};
+  return qpk::dense_kernel_name(names, n);
 }
 
 extern "C" hipError_t qpk_launch_jvp(const qpk::JvpArgs* a, int tiled, hipStream_t stream) {

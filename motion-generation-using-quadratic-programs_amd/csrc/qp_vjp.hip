@@ -32,13 +32,11 @@
 // nothing of its own (in the lane kernel's QP-major form it stays to help store the others'
 // blocks).  The box entry generates the columns of CI = [-I, +I] (-1.0 among -0.0, +1.0
 // among +0.0, as BoxProblems.to_dense() materialises them) and runs the same arithmetic: it reads
-// no CI and writes no dCI.
-#include <mutex>
-#include <set>
+// no CI and writes no dCI.  The substitutions, the group's factorisation and the launch are
+// qp_dense.h's, shared with qp_jvp.hip.
 #include <type_traits>
-#include <utility>
 
-#include "qp_common.h"
+#include "qp_dense.h"
 #include "qp_vjp.h"
 
 namespace qpk {
@@ -62,13 +60,6 @@ __device__ __forceinline__ void vjp_fill(const VjpArgs& g, int64_t b, double fv,
   fill(g.dhi, g.n);
   fill(g.dlo, g.n);
 }
-
-// element i of column j of CI = [-I, +I] (n x 2n)
-__device__ __forceinline__ double box_entry(int i, int j, int n) {
-  return j < n ? (i == j ? -1.0 : -0.0) : (i == j - n ? 1.0 : 0.0);
-}
-
-constexpr int tri(int i, int k) { return i * (i + 1) / 2 + k; }
 
 // The full form (qpgpu_vjp_full) is every kernel below built a second time with
 // FULL = true, on VjpFullArgs: g.gu joins r before the q x q solve, g.gf turns c into ct and a into
@@ -94,22 +85,6 @@ __device__ __forceinline__ double vjp_dg0(double a, double x, bool hasf, double 
 }
 
 // ---- one QP per lane ----------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void lane_fsub(const double (&L)[N * (N + 1) / 2], double (&v)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double s = v[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s = s - L[tri(i, k)] * v[k];
-    v[i] = s / L[tri(i, i)];
-  }
-}
-
-#define MS(i, t) Ms[((i) * N + (t)) * 64 + lane]
-#define SS(s, t) Ss[tri((s), (t)) * 64 + lane]
-#define CS(t) Cs[(t) * 64 + lane]
-#define WS(t) Ws[(t) * 64 + lane]
-
 // The arithmetic of QP b in one lane, L holding the lower triangle of its G: a into w, x into xv, c
 // into the lane's Cs slots (FULL with gf: ct = c + gfv * lam, once y is formed from c); the QP's
 // mode (anything but kVjpOk: nothing was computed).  Ms, Ss, Cs, Ws: the wave's LDS arrays; Lam
@@ -214,17 +189,7 @@ __device__ __forceinline__ int lane_solve(const VjpArgsOf<FULL>& g, int64_t b, i
       SS(i, j) = r / d;
     }
   }
-  // c = bsub(R, fsub(R, r)), in place
-  for (int i = 0; i < nq; i++) {
-    double s = CS(i);
-    for (int k = 0; k < i; k++) s = s - SS(i, k) * CS(k);
-    CS(i) = s / SS(i, i);
-  }
-  for (int i = nq - 1; i >= 0; i--) {
-    double s = CS(i);
-    for (int k = i + 1; k < nq; k++) s = s - SS(k, i) * CS(k);
-    CS(i) = s / SS(i, i);
-  }
+  lane_lds_solve(Ss, Cs, nq, lane);  // c = bsub(R, fsub(R, r)), in place
   // y = w - M c, a = bsub(L, y)
   for (int t = 0; t < nq; t++) {
     const double ct = CS(t);
@@ -456,68 +421,8 @@ __global__ void __launch_bounds__(64) vjp_lane_kernel(VjpArgsOf<FULL> g) {
     }
   }
 }
-#undef MS
-#undef SS
-#undef CS
-#undef WS
 
 // ---- one QP per group of S lanes -----------------------------------------------------------------
-// doubles of LDS per group: three S x (S + 1) tiles, four vectors, the working list (S ints)
-template <int S>
-constexpr int vjp_group_doubles() {
-  return 3 * S * (S + 1) + 4 * S + S / 2;
-}
-
-// A = chol(A) in place on rows and columns [0, size) of a tile; lane sl owns row sl.  `bound` (>= size)
-// is the trip count, the same in every lane of the wave.
-template <int S>
-__device__ __forceinline__ void group_chol(double* A, int size, int bound, int sl, int base) {
-  constexpr int LD = S + 1;
-  for (int j = 0; j < bound; j++) {
-    double s = A[sl * LD + j];
-    for (int k = 0; k < j; k++) s = s - A[sl * LD + k] * A[j * LD + k];
-    const double sq = sqrt(s);
-    const double d = __shfl(sq, base + j, 64);  // lane j's: the pivot
-    const double val = sl == j ? sq : s / d;
-    if (j < size && sl >= j && sl < size) A[sl * LD + j] = val;
-    sg_sync();
-  }
-}
-
-// lane i's element of fsub(A, rhs) (rhs: lane i's element); z is the group's scratch vector
-template <int S>
-__device__ __forceinline__ double group_fsub(const double* A, int size, int bound, int sl, double rhs, double* z) {
-  constexpr int LD = S + 1;
-  double out = 0.0;
-  for (int i = 0; i < bound; i++) {
-    if (sl == i && i < size) {
-      double s = rhs;
-      for (int k = 0; k < i; k++) s = s - A[i * LD + k] * z[k];
-      out = s / A[i * LD + i];
-      z[i] = out;
-    }
-    sg_sync();
-  }
-  return out;
-}
-
-// the same for bsub(A, rhs): A^T z = rhs
-template <int S>
-__device__ __forceinline__ double group_bsub(const double* A, int size, int bound, int sl, double rhs, double* z) {
-  constexpr int LD = S + 1;
-  double out = 0.0;
-  for (int i = bound - 1; i >= 0; i--) {
-    if (sl == i && i < size) {
-      double s = rhs;
-      for (int k = i + 1; k < size; k++) s = s - A[k * LD + i] * z[k];
-      out = s / A[i * LD + i];
-      z[i] = out;
-    }
-    sg_sync();
-  }
-  return out;
-}
-
 template <int T, int S, bool BOX, bool FULL>
 __global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgsOf<FULL> g) {
   extern __shared__ double vjp_lds[];
@@ -525,7 +430,7 @@ __global__ void __launch_bounds__(64) vjp_group_kernel(VjpArgsOf<FULL> g) {
   const int lane = threadIdx.x, sub = lane / S, sl = lane % S, base = sub * S;
   const int64_t b = g.qp0 + (int64_t)blockIdx.x * (64 / S) + sub;
   if (b >= g.batch) return;  // whole groups; the others never wait for them
-  double* Lm = vjp_lds + sub * vjp_group_doubles<S>();
+  double* Lm = vjp_lds + sub * group_doubles<S>();
   double* Mm = Lm + S * LD;
   double* Sm = Mm + S * LD;
   double* xs = Sm + S * LD;
@@ -701,22 +606,6 @@ static VjpKernel<FULL> group_kernel_of(int n) {
                    : vjp_group_kernel<T, 64, BOX, FULL>;
 }
 
-// Dynamic LDS beyond 64 KiB is granted once per kernel and device; host threads may launch
-// concurrently (include/qpgpu.h), so the record is locked.
-static hipError_t grant_lds(const void* k, size_t bytes) {
-  static std::mutex mu;
-  static std::set<std::pair<const void*, int>> granted;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const std::pair<const void*, int> key(k, dev);
-  std::lock_guard<std::mutex> lk(mu);
-  if (granted.count(key)) return hipSuccess;
-  e = hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) granted.insert(key);
-  return e;
-}
-
 template <bool FULL>
 static hipError_t launch_vjp(const VjpArgsOf<FULL>* a, int tiled, hipStream_t stream) {
   const int n = a->n;
@@ -729,45 +618,22 @@ static hipError_t launch_vjp(const VjpArgsOf<FULL>* a, int tiled, hipStream_t st
   else
     k = tiled ? (box ? group_kernel_of<64, true, FULL>(n) : group_kernel_of<64, false, FULL>(n))
               : (box ? group_kernel_of<1, true, FULL>(n) : group_kernel_of<1, false, FULL>(n));
-  const int S = n <= 16 ? 16 : n <= 32 ? 32 : 64;
-  const int64_t per_wg = lane ? 64 : 64 / S;  // QPs per workgroup (one wavefront)
-  size_t lds = 0;
-  if (!lane) {
-    const int per = S == 16 ? vjp_group_doubles<16>() : S == 32 ? vjp_group_doubles<32>() : vjp_group_doubles<64>();
-    lds = (size_t)per * (64 / S) * sizeof(double);
-    if (lds > 65536) {  // S = 64: beyond the default limit, inside the CU's 160 KiB
-      const hipError_t e = grant_lds(reinterpret_cast<const void*>(k), lds);
-      if (e != hipSuccess) return e;
-    }
-  }
-  VjpArgsOf<FULL> c = *a;
-  const int64_t per = (int64_t)1 << 30;  // workgroups per launch: the grid stays inside 32 bits
-  for (int64_t w0 = 0; w0 * per_wg < a->batch; w0 += per) {
-    c.qp0 = w0 * per_wg;
-    const int64_t left = (a->batch - c.qp0 + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(k, dim3((unsigned)(left < per ? left : per)), dim3(64), lds, stream, c);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return launch_dense(k, a, stream);
 }
 
 }  // namespace qpk
 
 extern "C" const char* qpk_vjp_name(int n) {
-  static const char* const lane[] = {"vjp_lane_n1", "vjp_lane_n2", "vjp_lane_n3", "vjp_lane_n4",
-                                     "vjp_lane_n5", "vjp_lane_n6", "vjp_lane_n7", "vjp_lane_n8"};
-  if (n < 1 || n > 64) return nullptr;
-  if (n <= 8) return lane[n - 1];
-  return n <= 16 ? "vjp_group_s16" : n <= 32 ? "vjp_group_s32" : "vjp_group_s64";
+  static const char* const names[] = {"vjp_lane_n1", "vjp_lane_n2", "vjp_lane_n3",   "vjp_lane_n4",   "vjp_lane_n5",  "vjp_lane_n6",
+                                      "vjp_lane_n7", "vjp_lane_n8", "vjp_group_s16", "vjp_group_s32", "vjp_group_s64"};
+  return qpk::dense_kernel_name(names, n);
 }
 
 extern "C" const char* qpk_vjp_full_name(int n) {
-  static const char* const lane[] = {"vjp_full_lane_n1", "vjp_full_lane_n2", "vjp_full_lane_n3", "vjp_full_lane_n4",
-                                     "vjp_full_lane_n5", "vjp_full_lane_n6", "vjp_full_lane_n7", "vjp_full_lane_n8"};
-  if (n < 1 || n > 64) return nullptr;
-  if (n <= 8) return lane[n - 1];
-  return n <= 16 ? "vjp_full_group_s16" : n <= 32 ? "vjp_full_group_s32" : "vjp_full_group_s64";
+  static const char* const names[] = {"vjp_full_lane_n1",   "vjp_full_lane_n2",   "vjp_full_lane_n3",  "vjp_full_lane_n4",
+                                      "vjp_full_lane_n5",   "vjp_full_lane_n6",   "vjp_full_lane_n7",  "vjp_full_lane_n8",
+                                      "vjp_full_group_s16", "vjp_full_group_s32", "vjp_full_group_s64"};
+  return qpk::dense_kernel_name(names, n);
 }
 
 extern "C" hipError_t qpk_launch_vjp(const qpk::VjpArgs* a, int tiled, hipStream_t stream) {

@@ -35,7 +35,7 @@
 // turns c into ct and a into ah in the outputs.  Each is a branch on the pointer, uniform over the
 // launch, and a NULL pointer leaves this build's operations (no + 0.0 is added: it would turn a -0.0
 // into +0.0).  Without the macro the translation unit is the text it was.
-#include "qp_common.h"
+#include "qp_dense.h"  // box_entry
 #include "qp_vjp.h"
 
 #ifndef QPGPU_VJP_FULL
@@ -67,10 +67,6 @@ struct VjpWsArgs {
   double* ws;
   int64_t per;  // doubles per slot
 };
-
-__device__ __forceinline__ double ws_box_entry(int i, int j, int n) {
-  return j < n ? (i == j ? -1.0 : -0.0) : (i == j - n ? 1.0 : 0.0);
-}
 
 // A = chol(A): init(i, j) is A[i][j] (i >= j), the factor goes to Lc (column-major, leading
 // dimension ld), which may be where init reads from.  scratch: kWsLanes * kJB + kJB * (kJB + 1).
@@ -360,7 +356,7 @@ __global__ void __launch_bounds__(kWsLanes) vjp_ws_kernel(VjpWsArgs w) {
       else if (t < p)
         s = g.CE[qCE + ((int64_t)i * p + t) * T];
       else if constexpr (BOX)
-        s = ws_box_entry(i, wi[t], n);
+        s = box_entry(i, wi[t], n);
       else
         s = g.CI[qCI + ((int64_t)i * m + wi[t]) * T];
       Mw[(int64_t)i * ldm + t] = s;

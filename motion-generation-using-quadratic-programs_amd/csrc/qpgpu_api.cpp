@@ -544,9 +544,9 @@ int qpgpu_kkt_residuals_box(const qpgpu_problem_desc* d, const double* G, const 
 // ---- the backward step (include/qpgpu.h; kernels: qp_vjp.hip) -------------------------
 // Both entries: every rule is decided from the descriptor and the pointers' values, before any
 // array is read; no workspace, one kernel, so the first call for a shape can be captured.
-// The argument rules of all four entries, in the header's order.
-static int vjp_rules(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
-                     const double* CI, const double* x, const double* u, const double* gx) {
+// The argument rules that the backward and the forward entries share, in the header's order.
+static int sens_rules(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                      const double* CI, const double* x, const double* u) {
   if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
   if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
   if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
@@ -555,12 +555,33 @@ static int vjp_rules(const qpgpu_problem_desc* d, bool box, const double* G, con
   if (box && (int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
   if ((int64_t)d->p + d->m > 0 && !u) return QPGPU_ERR_INVALID_ARGUMENT;
   if (d->batch > 0) {
-    if (!G || !x || !gx) return QPGPU_ERR_INVALID_ARGUMENT;
+    if (!G || !x) return QPGPU_ERR_INVALID_ARGUMENT;
     if (d->p > 0 && !CE) return QPGPU_ERR_INVALID_ARGUMENT;
     if (!box && d->m > 0 && !CI) return QPGPU_ERR_INVALID_ARGUMENT;
   }
   return QPGPU_SUCCESS;
 }
+
+// The argument rules of the backward entries: the shared ones, and gx.
+static int vjp_rules(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                     const double* CI, const double* x, const double* u, const double* gx) {
+  const int rc = sens_rules(d, box, G, CE, CI, x, u);
+  if (rc) return rc;
+  return (d->batch > 0 && !gx) ? QPGPU_ERR_INVALID_ARGUMENT : QPGPU_SUCCESS;
+}
+
+// The kernels' argument block: the arrays of the other kind of CI are dropped.
+static qpk::VjpArgs vjp_args(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
+                             const double* CI, const double* x, const double* u, const int32_t* status,
+                             const double* gx, double* dG, double* dg0, double* dCE, double* dce0, double* dCI,
+                             double* dci0, double* dhi, double* dlo) {
+  return {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
+          dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
+          box ? dlo : nullptr};
+}
+
+// a kernel's name for the qpgpu_kernel_name_* entries: the first that exists, else ""
+static const char* name_or_empty(const char* k, const char* k2 = nullptr) { return k ? k : k2 ? k2 : ""; }
 
 // a per-QP block is indexed with 32 bits
 static bool vjp_sizes_fit(const qpgpu_problem_desc* d) {
@@ -578,9 +599,7 @@ static int vjp_run(const qpgpu_problem_desc* d, bool box, const double* G, const
   // n <= 64: L, M and S of a QP fit on chip
   if (!qpk_vjp_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   if (d->batch == 0) return QPGPU_SUCCESS;
-  qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
-                    dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
-                    box ? dlo : nullptr};
+  const qpk::VjpArgs a = vjp_args(d, box, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, dhi, dlo);
   const int tiled = d->layout == QPGPU_LAYOUT_TILED64;
   hipError_t e;
   if (full) {
@@ -605,12 +624,7 @@ int qpgpu_vjp_box(const qpgpu_problem_desc* d, const double* G, const double* CE
   return vjp_run(d, true, G, CE, nullptr, x, u, status, gx, dG, dg0, dCE, dce0, nullptr, nullptr, dhi, dlo, stream);
 }
 
-const char* qpgpu_kernel_name_vjp(int32_t n, int32_t p, int32_t m) {
-  (void)p;
-  (void)m;
-  const char* k = qpk_vjp_name(n);
-  return k ? k : "";
-}
+const char* qpgpu_kernel_name_vjp(int32_t n, int32_t, int32_t) { return name_or_empty(qpk_vjp_name(n)); }
 
 // ---- the backward step with a caller's workspace (kernel for 64 < n <= 256: qp_vjp_ws.hip) --------
 // n <= 64 is vjp_run itself.  Beyond, the workspace rules follow the shape rule, all before the
@@ -629,9 +643,7 @@ static int vjp_ws_run(const qpgpu_problem_desc* d, bool box, const double* G, co
   const int64_t per = qpk_vjp_ws_doubles(d->n) * (int64_t)sizeof(double);
   if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || workspace_bytes < per)
     return QPGPU_ERR_INVALID_ARGUMENT;
-  qpk::VjpArgs a = {d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status, gx,
-                    dG, dg0, dCE, dce0, box ? nullptr : dCI, box ? nullptr : dci0, box ? dhi : nullptr,
-                    box ? dlo : nullptr};
+  const qpk::VjpArgs a = vjp_args(d, box, G, CE, CI, x, u, status, gx, dG, dg0, dCE, dce0, dCI, dci0, dhi, dlo);
   const int tiled = d->layout == QPGPU_LAYOUT_TILED64;
   hipError_t e;
   if (full) {
@@ -670,12 +682,8 @@ int qpgpu_vjp_box_ws(const qpgpu_problem_desc* d, const double* G, const double*
                     workspace, workspace_bytes, stream);
 }
 
-const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t p, int32_t m) {
-  (void)p;
-  (void)m;
-  const char* k = qpk_vjp_name(n);
-  if (!k) k = qpk_vjp_ws_name(n);
-  return k ? k : "";
+const char* qpgpu_kernel_name_vjp_ws(int32_t n, int32_t, int32_t) {
+  return name_or_empty(qpk_vjp_name(n), qpk_vjp_ws_name(n));
 }
 
 // ---- the full backward step: cotangents on u and f too ----------------------------
@@ -697,34 +705,20 @@ int qpgpu_vjp_box_full(const qpgpu_problem_desc* d, const double* G, const doubl
                     workspace, workspace_bytes, stream, true, gu, gf);
 }
 
-const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t p, int32_t m) {
-  (void)p;
-  (void)m;
-  const char* k = qpk_vjp_full_name(n);
-  if (!k) k = qpk_vjp_ws_full_name(n);
-  return k ? k : "";
+const char* qpgpu_kernel_name_vjp_full(int32_t n, int32_t, int32_t) {
+  return name_or_empty(qpk_vjp_full_name(n), qpk_vjp_ws_full_name(n));
 }
 
 // ---- forward-mode sensitivities (include/qpgpu.h; kernels: qp_jvp.hip) ---------------
-// The rules are vjp_rules' without gx, in the same order, decided before any array is read; no
-// workspace, one kernel, so the first call for a shape can be captured.
+// The rules are sens_rules, decided before any array is read; no workspace, one kernel, so the
+// first call for a shape can be captured.
 static int jvp_run(const qpgpu_problem_desc* d, bool box, const double* G, const double* CE,
                    const double* CI, const double* x, const double* u, const int32_t* status,
                    const double* tG, const double* tg0, const double* tCE, const double* tce0,
                    const double* tCI, const double* tci0, const double* thi, const double* tlo, double* tx,
                    double* tu, double* tf, void* stream) {
-  if (!d) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->n <= 0 || d->p < 0 || d->m < 0 || d->batch < 0) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->layout != QPGPU_LAYOUT_QP_MAJOR && d->layout != QPGPU_LAYOUT_TILED64)
-    return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->flags != 0) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (box && (int64_t)d->m != 2 * (int64_t)d->n) return QPGPU_ERR_INVALID_ARGUMENT;
-  if ((int64_t)d->p + d->m > 0 && !u) return QPGPU_ERR_INVALID_ARGUMENT;
-  if (d->batch > 0) {
-    if (!G || !x) return QPGPU_ERR_INVALID_ARGUMENT;
-    if (d->p > 0 && !CE) return QPGPU_ERR_INVALID_ARGUMENT;
-    if (!box && d->m > 0 && !CI) return QPGPU_ERR_INVALID_ARGUMENT;
-  }
+  const int rc = sens_rules(d, box, G, CE, CI, x, u);
+  if (rc) return rc;
   // n <= 64: L, M and S of a QP fit on chip
   if (!qpk_jvp_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   if (d->batch == 0 || (!tx && !tu && !tf)) return QPGPU_SUCCESS;
@@ -752,12 +746,7 @@ int qpgpu_jvp_box(const qpgpu_problem_desc* d, const double* G, const double* CE
                  stream);
 }
 
-const char* qpgpu_kernel_name_jvp(int32_t n, int32_t p, int32_t m) {
-  (void)p;
-  (void)m;
-  const char* k = qpk_jvp_name(n);
-  return k ? k : "";
-}
+const char* qpgpu_kernel_name_jvp(int32_t n, int32_t, int32_t) { return name_or_empty(qpk_jvp_name(n)); }
 
 // Host-pointer entry (the drop-in's path, one QP per solve_quadprog() call, and the batched
 // controller's).  Device buffers are one allocation per thread, laid out

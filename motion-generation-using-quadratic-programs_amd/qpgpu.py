@@ -668,9 +668,43 @@ class _DeviceBatchBase:
                                              ctypes.c_void_p(stream.cuda_stream)), self._ENTRY_KKT)
         return r
 
-    def _vjp_elems(self, name):
+    def _vjp_shape(self, name):
         n, p, m = self.n, self.p, self.m
-        return {"dG": n * n, "dg0": n, "dCE": n * p, "dce0": p, "dCI": n * m, "dci0": m, "dhi": n, "dlo": n}[name]
+        return {"dG": (n, n), "dg0": (n,), "dCE": (n, p), "dce0": (p,), "dCI": (n, m), "dci0": (m,),
+                "dhi": (n,), "dlo": (n,)}[name]
+
+    def _vjp_elems(self, name):
+        return math.prod(self._vjp_shape(name))
+
+    def _sens_call(self, entry, names, shape, outs, status, stream, x):
+        """What vjp() and jvp() share: x and stream by default, the outputs `names` of `entry` as
+        `outs` selects them (a tensor, or True for a new one of shape(name, rows)), the status
+        selection, the descriptor.  Returns (x, stream, outs, st, d, vp), vp turning a tensor or
+        None into a ctypes argument."""
+        import torch
+
+        x = self.x if x is None else x
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        rows = x.numel() // self.n
+        outs = dict.fromkeys(names, True) if outs is None else dict(outs)
+        for k in outs:
+            if k not in names:
+                raise ValueError(f"{k!r} is no output of {entry}: {names}")
+            if outs[k] is True:
+                outs[k] = torch.empty(shape(k, rows), dtype=torch.float64, device=x.device)
+        st = self.status if status is True else (None if status is None or status is False else status)
+        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        return x, stream, outs, st, d, vp
+
+    def _rows(self, t, shape):
+        """A host copy of a device array of one `shape` block per QP as numpy (batch, *shape),
+        whatever the layout."""
+        h = t.cpu().numpy().reshape(-1)
+        if self.layout == LAYOUT_TILED64:
+            return from_tiled64(h, self.batch, shape)
+        return h[:self.batch * math.prod(shape)].reshape((self.batch,) + shape)
 
     def vjp(self, u, gx, outs=None, status=True, stream=None, x=None, slots=VJP_SLOTS, workspace=None,
             gu=None, gf=None):
@@ -690,19 +724,8 @@ class _DeviceBatchBase:
         goes to qpgpu_vjp_full / qpgpu_vjp_box_full, the backward step of a loss l(x, u, f)."""
         import torch
 
-        x = self.x if x is None else x
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        rows = x.numel() // self.n
-        outs = dict.fromkeys(self._VJP_OUTPUTS, True) if outs is None else dict(outs)
-        for k in outs:
-            if k not in self._VJP_OUTPUTS:
-                raise ValueError(f"{k!r} is no output of {self._ENTRY_VJP}: {self._VJP_OUTPUTS}")
-            if outs[k] is True:
-                outs[k] = torch.empty((rows, self._vjp_elems(k)), dtype=torch.float64, device=x.device)
-        st = self.status if status is True else (None if status is None or status is False else status)
-        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        x, stream, outs, st, d, vp = self._sens_call(
+            self._ENTRY_VJP, self._VJP_OUTPUTS, lambda k, rows: (rows, self._vjp_elems(k)), outs, status, stream, x)
         tensors = [getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st, gx] + [outs.get(k) for k in self._VJP_OUTPUTS]
         full = gu is not None or gf is not None
         if full:
@@ -728,17 +751,7 @@ class _DeviceBatchBase:
     def vjp_rows(self, outs):
         """A vjp() result as numpy arrays shaped like the inputs ((batch, n, n) for dG, ...),
         whatever the layout."""
-        n, p, m = self.n, self.p, self.m
-        shapes = {"dG": (n, n), "dg0": (n,), "dCE": (n, p), "dce0": (p,), "dCI": (n, m), "dci0": (m,),
-                  "dhi": (n,), "dlo": (n,)}
-        res = {}
-        for k, t in outs.items():
-            h = t.cpu().numpy().reshape(-1)
-            if self.layout == LAYOUT_TILED64:
-                res[k] = from_tiled64(h, self.batch, shapes[k])
-            else:
-                res[k] = h[:self.batch * self._vjp_elems(k)].reshape((self.batch,) + shapes[k])
-        return res
+        return {k: self._rows(t, self._vjp_shape(k)) for k, t in outs.items()}
 
     def jvp(self, u, tangents, outs=None, status=True, stream=None, x=None):
         """Enqueue the forward-mode sensitivities (qpgpu_jvp / qpgpu_jvp_box, include/qpgpu.h) of this
@@ -750,25 +763,11 @@ class _DeviceBatchBase:
         name to the tensor to write, or True to allocate it: an output that is not named is passed
         as NULL and not computed.  Returns the dict of the tensors written: tx (rows, n) and tu
         (rows, p + m) in this batch's layout, tf (batch,) (jvp_rows() decodes host copies)."""
-        import torch
-
-        x = self.x if x is None else x
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
         for k in tangents:
             if k not in self._JVP_TANGENTS:
                 raise ValueError(f"{k!r} is no tangent of {self._ENTRY_JVP}: {self._JVP_TANGENTS}")
-        rows = x.numel() // self.n
-        shapes = {"tx": (rows, self.n), "tu": (rows, self.p + self.m), "tf": (self.batch,)}
-        outs = dict.fromkeys(JVP_OUTPUTS, True) if outs is None else dict(outs)
-        for k in outs:
-            if k not in JVP_OUTPUTS:
-                raise ValueError(f"{k!r} is no output of {self._ENTRY_JVP}: {JVP_OUTPUTS}")
-            if outs[k] is True:
-                outs[k] = torch.empty(shapes[k], dtype=torch.float64, device=x.device)
-        st = self.status if status is True else (None if status is None or status is False else status)
-        d = ProblemDesc(self.n, self.p, self.m, 0, self.batch, 0, self.layout)
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        shape = lambda k, rows: {"tx": (rows, self.n), "tu": (rows, self.p + self.m), "tf": (self.batch,)}[k]
+        x, stream, outs, st, d, vp = self._sens_call(self._ENTRY_JVP, JVP_OUTPUTS, shape, outs, status, stream, x)
         tensors = ([getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st] + [tangents.get(k) for k in self._JVP_TANGENTS]
                    + [outs.get(k) for k in JVP_OUTPUTS])
         _check(getattr(LIB, self._ENTRY_JVP)(ctypes.byref(d), *[vp(t) for t in tensors],
@@ -779,23 +778,12 @@ class _DeviceBatchBase:
         """A jvp() result as numpy arrays: tx (batch, n), tu (batch, p + m), tf (batch,), whatever the
         layout."""
         shapes = {"tx": (self.n,), "tu": (self.p + self.m,)}
-        res = {}
-        for k, t in outs.items():
-            h = t.cpu().numpy().reshape(-1)
-            if k == "tf":
-                res[k] = h[:self.batch].copy()
-            elif self.layout == LAYOUT_TILED64:
-                res[k] = from_tiled64(h, self.batch, shapes[k])
-            else:
-                res[k] = h[:self.batch * shapes[k][0]].reshape((self.batch,) + shapes[k])
-        return res
+        return {k: t.cpu().numpy().reshape(-1)[:self.batch].copy() if k == "tf" else self._rows(t, shapes[k])
+                for k, t in outs.items()}
 
     def kkt_rows(self, r):
         """A kkt_residuals() result as numpy (batch, 8), whatever the layout."""
-        rh = r.cpu().numpy()
-        if self.layout == LAYOUT_TILED64:
-            return from_tiled64(rh.reshape(-1), self.batch, (KKT_NRES,))
-        return rh.reshape(-1, KKT_NRES)[:self.batch]
+        return self._rows(r, (KKT_NRES,))
 
     def results(self):
         it = None if self.iters is None else self.iters.cpu().numpy()
