@@ -182,6 +182,106 @@ __device__ __forceinline__ void for_seq(F&& f) {
 // ---- arithmetic of the fast build (frcp, rcp_ok, ldiv_r, ldiv, ldistance): qp_common.h,
 // shared with the lane-pair kernel (qp_pair.hip).
 
+// What lane_body's kResident kernel keeps on the lane through its loop: the CI rows past the LDS copy
+// (VGPRs), ci0 and the rollback copy of x (AGPRs).  Three unused bytes in every other instantiation.
+template <bool ON, int ROWS, int NM, int MM>
+struct LaneResident {
+  double kept[ROWS][MM];
+  AgprD ci0_ag[MM], xold_ag[NM];
+};
+template <int ROWS, int NM, int MM>
+struct LaneResident<false, ROWS, NM, MM> {
+  char kept, ci0_ag, xold_ag;
+};
+
+// One l1 pass of the kernel that keeps the late CI rows on the lane (lane_body's kResident, the
+// QP-major one-free full-wave kernel): s = CI^T x + ci0 with rows 0..ROWS-1 of CI from the LDS
+// copy, rows ROWS..NM-1 from the VGPRs kept[0..NM-ROWS) and ci0 from the AGPRs ci0_ag (the select
+// never reads ci0, so it is read back once per scan, into the registers the LDS rows have left).
+// LOAD (the first pass, peeled out of the loop) fills both from global memory first, as dwordx4
+// under the scan's own predicate; later passes issue no global load.  The same sums in the same
+// order as lane_body's scan_pass: every s[i] sums j ascending from 0.0, then + ci0[i]; psi and
+// the optimality test are scan_pass's.
+// The LDS rows are read one row ahead of their sums and fenced from the scheduler.  Left alone
+// it issues all ROWS rows' reads at once, and with the kept rows live across the whole loop the
+// allocator then moves column NM - 1 of J through AGPRs, in the loop and in every step of the
+// equality phase.  The first pass reads no row ahead: it waits for its global loads anyway, and
+// ci0 is still in VGPRs there.
+template <int NM, int MM, int ROWS, bool LOAD>
+__device__ __forceinline__ void lane_scan_kept(const double* sbuf, int lane, const double* CIg, const double* ci0g,
+                                               const double (&xv)[NM], double (&kept)[NM - ROWS][MM],
+                                               AgprD (&ci0_ag)[MM], double (&sv)[MM], double c1, double c2,
+                                               bool need_scan, bool& active, int& iter, uint64_t& excl, double& ss,
+                                               int& ip) {
+  const bool do_scan = active && need_scan;
+  if (!wave_any(do_scan)) return;
+  if (do_scan) {
+    iter++;
+    double c0[MM];
+    if constexpr (LOAD) {
+#pragma unroll
+      for (int r = ROWS; r <= NM; r++) {
+        const double* src = r < NM ? CIg + r * MM : ci0g;
+#pragma unroll
+        for (int i = 0; i < MM; i += 2) {
+          const double2 v = *reinterpret_cast<const double2*>(src + i);
+          (r < NM ? kept[r < NM ? r - ROWS : 0][i] : c0[i]) = v.x;
+          (r < NM ? kept[r < NM ? r - ROWS : 0][i + 1] : c0[i + 1]) = v.y;
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int i = 0; i < MM; i++) sv[i] = 0.0;
+    constexpr int AHEAD = LOAD ? 0 : 1;
+    double2 row[2][MM / 2];
+    auto ldrow = [&](int j, double2(&dst)[MM / 2]) {
+#pragma unroll
+      for (int i = 0; i < MM; i += 2)
+        dst[i / 2] = *reinterpret_cast<const double2*>(sbuf + (((j * MM + i) >> 1) * kQpw + lane) * 2);
+    };
+#pragma unroll
+    for (int j = 0; j < AHEAD; j++) ldrow(j, row[j % 2]);
+#pragma unroll
+    for (int j = 0; j < NM; j++) {
+      const double xj = xv[j];
+      if (j + AHEAD < ROWS) ldrow(j + AHEAD, row[(j + AHEAD) % 2]);
+      if constexpr (!LOAD) {
+        if (j == ROWS) {
+#pragma unroll
+          for (int i = 0; i < MM; i++) c0[i] = from_agpr(ci0_ag[i]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < ROWS) {
+#pragma unroll
+        for (int i = 0; i < MM; i += 2) {
+          sv[i] += row[j % 2][i / 2].x * xj;
+          sv[i + 1] += row[j % 2][i / 2].y * xj;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < MM; i++) sv[i] += kept[j >= ROWS ? j - ROWS : 0][i] * xj;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    double psi = 0.0;
+#pragma unroll
+    for (int i = 0; i < MM; i++) {
+      sv[i] += c0[i];
+      psi += (sv[i] < 0.0) ? sv[i] : 0.0;
+    }
+    if constexpr (LOAD) {
+#pragma unroll
+      for (int i = 0; i < MM; i++) ci0_ag[i] = to_agpr(c0[i]);
+    }
+    excl = 0;
+    ss = 0.0;
+    ip = 0;
+    if (fabs(psi) <= (double)MM * kEps * c1 * c2 * 100.0) active = false;  // optimal
+  }
+}
+
 // PX >= 0: p is the compile-time constant PX as well (C1/C4: 6, C2: 0), which folds every
 // [p, iq) loop of the active-set phase (for n = 7, p = 6 that range holds at most one entry).
 // The solve of one wave's 64 QPs.  SAFE: the IEEE forms of division and distance (the exact
@@ -1283,18 +1383,53 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, LdsD* lds) {
     };
     uint64_t tscan = 0, tsel = 0, nloop = 0, tfirst = 0;  // diagnostic stamps only
     [[maybe_unused]] uint64_t tdzr = 0, tstep = 0;        // (QPGPU_LANE_STAMPS == 2: l2a split)
+    // kResident (the QP-major one-free kernel, qp_lane_full_kernel<7, 14, 1, 6>): the CI rows past
+    // the LDS copy stay in VGPRs (kept) and ci0 in AGPRs (ci0_ag) from the first scan to the end of
+    // the loop, so no pass after the first issues a global load: the later scans sum from the
+    // registers, and the select picks np's late rows out of kept under its own `take` (below).
+    // The rollback copy of x, which only a rollback reads, is parked in AGPRs too (xold_ag; set
+    // once ahead of the loop so that it is defined on entry).  Without the two parkings and the
+    // scan's row-ahead fence the allocator moves column NM - 1 of J through AGPRs in every step of
+    // the equality phase.  The first scan is peeled out of the loop, which then runs select,
+    // step, next scan: the kept rows are defined in straight-line code ahead of the loop instead
+    // of being a loop-carried value with an undefined entry.  Every lane that is ever active scans
+    // in that first pass (need_scan starts true), so nothing else needs a load path.  The scan is
+    // lane_scan_kept, a function of its own and not a lambda here, so that the other instantiations
+    // of lane_body are the code they were.
+    constexpr bool kResident = kOneFree && kCiDma;
+    constexpr int kKept = kResident ? NM - kCiRows : 1;
+    // (the full-wave DMA path always completes for such a shape, so ci_ready is true at the loop)
+    static_assert(!kResident || (kQpw * NM * PX + 127) / 128 * 128 + kQpw * PX <= STAGE,
+                  "the kept-row scan reads the LDS copy the DMA path fills");
+    [[maybe_unused]] LaneResident<kResident, kKept, NM, MM> res;
+    [[maybe_unused]] auto& kept = res.kept;
+    [[maybe_unused]] auto& ci0_ag = res.ci0_ag;
+    [[maybe_unused]] auto& xold_ag = res.xold_ag;
+    // (stamps: nloop counts the passes as the unpeeled loop does, one per scan position reached
+    // with a lane still active)
+    if constexpr (kResident) {
+      const uint64_t ts0 = (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
+      if (kStamps && a.stamps && wave_any(active)) nloop = 1;
+      lane_scan_kept<NM, MM, kCiRows, true>(sbuf, lane, CIg, ci0g, xv, kept, ci0_ag, sv, c1, c2, need_scan, active,
+                                            iter, excl, ss, ip);
+      if (kStamps && a.stamps) tfirst = tscan = __builtin_amdgcn_s_memtime() - ts0;
+#pragma unroll
+      for (int i = 0; i < NM; i++) xold_ag[i] = to_agpr(xv[i]);
+    }
     while (wave_any(active)) {
       if constexpr (F) {
         if (wave_any(!fok)) return false;
       }
       const uint64_t tl0 = (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
-      scan_pass();
-      const uint64_t tl1 = (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
-      if (kStamps && a.stamps) {
-        tscan += tl1 - tl0;
-        if (nloop == 0) tfirst = tl1 - tl0;
+      if constexpr (!kResident) scan_pass();
+      const uint64_t tl1 = kResident ? tl0 : (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
+      if constexpr (!kResident) {
+        if (kStamps && a.stamps) {
+          tscan += tl1 - tl0;
+          if (nloop == 0) tfirst = tl1 - tl0;
+        }
+        nloop++;
       }
-      nloop++;
       // kOneFree: select and step of one pass, the general ones below restated for n - p = 1.  Then
       // iq is S = n - 1 or S + 1, and of the general machinery only this is ever reached:
       //   * add_constraint and delete_constraint rotate nothing (their Givens loops run over j >= S + 1
@@ -1326,17 +1461,32 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, LdsD* lds) {
             const bool take = sv[i] < ss && !((blocked >> i) & 1u);
             ss = take ? sv[i] : ss;
             ip = take ? i : ip;
+            // kResident: np's rows past the LDS copy ride the same chain, out of the kept rows,
+            // so that np = CI[:, ip] without a load.  Exact because (1) np persists across the
+            // passes that do not select (the dual step's re-add of the pending ip), (2) a
+            // re-select after a rollback in which no candidate is taken keeps ip, and with it
+            // these rows of np, and (3) a scan resets ss and ip, so the first take after it (one
+            // fires whenever the select goes on to a step: ss < 0) rewrites both rows.
+            if constexpr (kResident) {
+#pragma unroll
+              for (int j = kCiRows; j < NM; j++) npv[j] = take ? kept[j - kCiRows < kKept ? j - kCiRows : 0][i] : npv[j];
+            }
           }
           if (ss >= 0.0) {
             active = false;  // optimal
           } else {
 #pragma unroll
-            for (int j = 0; j < NM; j++)
+            for (int j = 0; j < (kResident ? kCiRows : NM); j++)
               npv[j] = (j < kCiRows && ci_ready) ? ci_lds_at(j * MM + ip) : ldCI(j * m + ip);
             // (ci0[ip] is not loaded: only the partial step's refresh reads it)
             // the rollback copy, under the loads: x is the scan's here, or the x a rollback restored
 #pragma unroll
-            for (int i = 0; i < NM; i++) xold[i] = xv[i];
+            for (int i = 0; i < NM; i++) {
+              if constexpr (kResident)
+                xold_ag[i] = to_agpr(xv[i]);
+              else
+                xold[i] = xv[i];
+            }
             if (iq == S) uv[S] = 0.0;  // (u[S + 1] = 0.0 is implied, A[iq] = ip is the slot's at the add)
           }
         }
@@ -1409,7 +1559,12 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, LdsD* lds) {
                 if (dd <= kEps * R_norm) {  // degenerate: roll back to the l1 state, select again
                   excl = (uint32_t)excl | (1u << ip);
 #pragma unroll
-                  for (int i = 0; i < NM; i++) xv[i] = xold[i];
+                  for (int i = 0; i < NM; i++) {
+                    if constexpr (kResident)
+                      xv[i] = from_agpr(xold_ag[i]);
+                    else
+                      xv[i] = xold[i];
+                  }
                   need_scan = false;
                   need_select = true;
                 } else {
@@ -1422,6 +1577,13 @@ __device__ __forceinline__ bool lane_body(const QpArgs& a, LdsD* lds) {
               }
             }
           }
+        }
+        if constexpr (kResident) {  // the next pass's scan, from the kept rows
+          const uint64_t ts0 = (kStamps && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
+          if (kStamps && a.stamps && wave_any(active)) nloop++;
+          lane_scan_kept<NM, MM, kCiRows, false>(sbuf, lane, CIg, ci0g, xv, kept, ci0_ag, sv, c1, c2, need_scan,
+                                                 active, iter, excl, ss, ip);
+          if (kStamps && a.stamps) tscan += __builtin_amdgcn_s_memtime() - ts0;
         }
         continue;
       }
