@@ -674,6 +674,53 @@ int qpgpu_jvp_box(const qpgpu_problem_desc* d,
  * 8 < n <= 64; "" for n > 64 or n <= 0. */
 const char* qpgpu_kernel_name_jvp(int32_t n, int32_t p, int32_t m);
 
+/* ---- K tangent directions on one factorisation ------------------------------------------------------
+ * qpgpu_jvp_many is qpgpu_jvp along K = ntan directions of the data of every QP in one launch: the
+ * Jacobian dx* / dg0 (n directions), a Gauss-Newton step, a sweep over a handful of parameters.  L, M,
+ * S and R do not depend on the direction and are computed once per QP.  Everything said at
+ * qpgpu_jvp / qpgpu_jvp_box holds unless stated here: device pointers, enqueue only, no allocation,
+ * no workspace (a first call can be captured into a hipGraph); both layouts, natural alignment and
+ * sub-ranges; the call writes the requested outputs of its own QPs and nothing else (no TILED64
+ * padding slot, no input); d->flags must be 0; status may be NULL; a masked QP gets +0.0 and one
+ * with q > n NaN in every requested output of all K directions; tangents of constraints outside W
+ * never enter the arithmetic and may hold NaN.
+ *
+ * Layout of the K directions: a tangent (or output) of an array whose per-QP block has E elements is
+ * an array whose per-QP block has K*E elements; direction k's element e is element k*E + e of that
+ * block, direction-major, in either layout (TILED64: X + (b/64)*64*K*E + (k*E + e)*64 + b%64).  So a
+ * QP-major tG is (batch, K, n, n), tx is K*n doubles per QP, tu K*(p + m) (K*(p + 2n) for box), and tf
+ * is K doubles per QP, a per-QP block of E = K in the layout of x (with K = 1: tf[b] in both layouts).
+ * Each tangent pointer may be NULL: a zero tangent for all K directions, whose [given] steps are
+ * not executed.  Each output may be NULL; with all three NULL the call is QPGPU_SUCCESS and nothing is
+ * launched.
+ *
+ * Definition: for every QP and every k < K, direction k's tx, tu and tf are bit for bit the
+ * qpgpu_jvp (qpgpu_jvp_box) definition applied to the k-th slice of each given tangent: every sum is
+ * the definition's, serial in its inner index, no FMA.  The results depend neither on K nor on how
+ * the directions are chunked; K = 1 has the bits of qpgpu_jvp.
+ *
+ * Argument rules, decided before any array is read, in this order: qpgpu_jvp's argument rules as
+ * they are; ntan < 1 is QPGPU_ERR_INVALID_ARGUMENT; then the shape rule, QPGPU_ERR_UNSUPPORTED_SHAPE for
+ * n > 64 and when any of ntan*n*n, ntan*n*p, ntan*n*m, ntan*(p + m) reaches 2^31; batch = 0 is
+ * QPGPU_SUCCESS after these. */
+int qpgpu_jvp_many(const qpgpu_problem_desc* d, int32_t ntan,
+                   const double* G, const double* CE, const double* CI,
+                   const double* x, const double* u, const int32_t* status,
+                   const double* tG, const double* tg0, const double* tCE, const double* tce0,
+                   const double* tCI, const double* tci0,
+                   double* tx, double* tu, double* tf, void* stream);
+int qpgpu_jvp_box_many(const qpgpu_problem_desc* d, int32_t ntan,
+                       const double* G, const double* CE,
+                       const double* x, const double* u, const int32_t* status,
+                       const double* tG, const double* tg0, const double* tCE, const double* tce0,
+                       const double* thi, const double* tlo,
+                       double* tx, double* tu, double* tf, void* stream);
+
+/* Name of the kernel a qpgpu_jvp_many / qpgpu_jvp_box_many launch of this shape runs: a name containing
+ * "jvp" and "many", and "lane" (one QP per lane) for n <= 8, "group" (one QP per 16, 32 or 64 lanes)
+ * for 8 < n <= 64; "" for n > 64 or n <= 0. */
+const char* qpgpu_kernel_name_jvp_many(int32_t n, int32_t p, int32_t m);
+
 /* qpgpu_solve_batched with HOST pointers: copies the inputs to the device, solves, copies the outputs back
  * and synchronises.  This is what the ArrayHH drop-in (libquadprog_amd.so) calls for each
  * solve_quadprog(); it always runs the HIP kernel (there is no CPU path in the product).

@@ -21,6 +21,7 @@
 #include "qp_common.h"
 #include "qp_kkt.h"
 #include "qp_jvp.h"
+#include "qp_jvp_many.h"
 #include "qp_vjp.h"
 
 extern "C" int qpk_medium_max_n(void);
@@ -747,6 +748,49 @@ int qpgpu_jvp_box(const qpgpu_problem_desc* d, const double* G, const double* CE
 }
 
 const char* qpgpu_kernel_name_jvp(int32_t n, int32_t, int32_t) { return name_or_empty(qpk_jvp_name(n)); }
+
+// ---- K directions on one factorisation (include/qpgpu.h; kernels: qp_jvp_many.hip) ---
+// sens_rules, then ntan, then the shape rule: a per-QP block of K directions is indexed with 32 bits.
+static int jvp_many_run(const qpgpu_problem_desc* d, int32_t ntan, bool box, const double* G, const double* CE,
+                        const double* CI, const double* x, const double* u, const int32_t* status,
+                        const double* tG, const double* tg0, const double* tCE, const double* tce0,
+                        const double* tCI, const double* tci0, const double* thi, const double* tlo, double* tx,
+                        double* tu, double* tf, void* stream) {
+  const int rc = sens_rules(d, box, G, CE, CI, x, u);
+  if (rc) return rc;
+  if (ntan < 1) return QPGPU_ERR_INVALID_ARGUMENT;
+  if (!qpk_jvp_many_name(d->n) || !vjp_sizes_fit(d)) return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  const int64_t lim = (int64_t)1 << 31, K = ntan, n = d->n;
+  if (K * n * n >= lim || K * n * d->p >= lim || K * n * d->m >= lim || K * ((int64_t)d->p + d->m) >= lim)
+    return QPGPU_ERR_UNSUPPORTED_SHAPE;
+  if (d->batch == 0 || (!tx && !tu && !tf)) return QPGPU_SUCCESS;
+  const qpk::JvpManyArgs a = {{d->n, d->p, d->m, box ? 1 : 0, d->batch, 0, G, CE, box ? nullptr : CI, x, u, status,
+                               tG, tg0, tCE, tce0, box ? nullptr : tCI, box ? nullptr : tci0, box ? thi : nullptr,
+                               box ? tlo : nullptr, tx, tu, tf},
+                              ntan};
+  const hipError_t e =
+      qpk_launch_jvp_many(&a, d->layout == QPGPU_LAYOUT_TILED64, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  return QPGPU_SUCCESS;
+}
+
+int qpgpu_jvp_many(const qpgpu_problem_desc* d, int32_t ntan, const double* G, const double* CE, const double* CI,
+                   const double* x, const double* u, const int32_t* status, const double* tG, const double* tg0,
+                   const double* tCE, const double* tce0, const double* tCI, const double* tci0, double* tx,
+                   double* tu, double* tf, void* stream) {
+  return jvp_many_run(d, ntan, false, G, CE, CI, x, u, status, tG, tg0, tCE, tce0, tCI, tci0, nullptr, nullptr, tx,
+                      tu, tf, stream);
+}
+
+int qpgpu_jvp_box_many(const qpgpu_problem_desc* d, int32_t ntan, const double* G, const double* CE, const double* x,
+                       const double* u, const int32_t* status, const double* tG, const double* tg0,
+                       const double* tCE, const double* tce0, const double* thi, const double* tlo, double* tx,
+                       double* tu, double* tf, void* stream) {
+  return jvp_many_run(d, ntan, true, G, CE, nullptr, x, u, status, tG, tg0, tCE, tce0, nullptr, nullptr, thi, tlo,
+                      tx, tu, tf, stream);
+}
+
+const char* qpgpu_kernel_name_jvp_many(int32_t n, int32_t, int32_t) { return name_or_empty(qpk_jvp_many_name(n)); }
 
 // Host-pointer entry (the drop-in's path, one QP per solve_quadprog() call, and the batched
 // controller's).  Device buffers are one allocation per thread, laid out

@@ -86,6 +86,9 @@ EXPORTED_SYMBOLS = (
     "qpgpu_jvp",
     "qpgpu_jvp_box",
     "qpgpu_kernel_name_jvp",
+    "qpgpu_jvp_many",
+    "qpgpu_jvp_box_many",
+    "qpgpu_kernel_name_jvp_many",
     "qpgpu_solve_batched_host",
     "qpgpu_max_n",
     "qpgpu_max_m",
@@ -170,6 +173,12 @@ def _load():
     lib.qpgpu_jvp_box.restype = ctypes.c_int
     lib.qpgpu_kernel_name_jvp.argtypes = [ctypes.c_int32] * 3
     lib.qpgpu_kernel_name_jvp.restype = ctypes.c_char_p
+    lib.qpgpu_jvp_many.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32] + [vp] * 16
+    lib.qpgpu_jvp_many.restype = ctypes.c_int
+    lib.qpgpu_jvp_box_many.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32] + [vp] * 15
+    lib.qpgpu_jvp_box_many.restype = ctypes.c_int
+    lib.qpgpu_kernel_name_jvp_many.argtypes = [ctypes.c_int32] * 3
+    lib.qpgpu_kernel_name_jvp_many.restype = ctypes.c_char_p
     lib.qpgpu_solve_batched_host.argtypes = [ctypes.POINTER(ProblemDesc)] + [vp] * 10
     lib.qpgpu_solve_batched_host.restype = ctypes.c_int
     lib.qpgpu_solve_batched_multi.argtypes = [ctypes.POINTER(ProblemDesc), ctypes.c_int32, vp] + [vp] * 10
@@ -270,6 +279,12 @@ def kernel_name_jvp(n: int, p: int = 0, m: int = 0) -> str:
     """The kernel a qpgpu_jvp / qpgpu_jvp_box launch of this shape runs: a name with "jvp", and "lane"
     for n <= 8, "group" for 8 < n <= 64; "" for n > 64 or n <= 0."""
     return LIB.qpgpu_kernel_name_jvp(n, p, m).decode()
+
+
+def kernel_name_jvp_many(n: int, p: int = 0, m: int = 0) -> str:
+    """The kernel a qpgpu_jvp_many / qpgpu_jvp_box_many launch of this shape runs: a name with "jvp" and
+    "many", and "lane" or "group"; "" for n > 64 or n <= 0."""
+    return LIB.qpgpu_kernel_name_jvp_many(n, p, m).decode()
 
 
 JVP_OUTPUTS = ("tx", "tu", "tf")
@@ -781,6 +796,37 @@ class _DeviceBatchBase:
         return {k: t.cpu().numpy().reshape(-1)[:self.batch].copy() if k == "tf" else self._rows(t, shapes[k])
                 for k, t in outs.items()}
 
+    def jvp_many(self, u, tangents, ntan, outs=None, status=True, stream=None, x=None):
+        """jvp() along ntan directions per QP in one launch (qpgpu_jvp_many / qpgpu_jvp_box_many,
+        include/qpgpu.h): the factorisations are shared by the directions, and direction k has the bits
+        of jvp() on slice k.  A tangent of an input with E elements per QP has ntan * E, direction-major
+        (QP-major: (batch, ntan, ...)), in this batch's layout; so have the outputs: tx (rows, ntan * n),
+        tu (rows, ntan * (p + m)), tf (rows, ntan) (jvp_many_rows() decodes host copies).  Everything else
+        as jvp() takes it."""
+        for k in tangents:
+            if k not in self._JVP_TANGENTS:
+                raise ValueError(f"{k!r} is no tangent of {self._ENTRY_JVP}_many: {self._JVP_TANGENTS}")
+        K = int(ntan)
+        shape = lambda k, rows: (rows, K * {"tx": self.n, "tu": self.p + self.m, "tf": 1}[k])
+        entry = self._ENTRY_JVP + "_many"
+        x, stream, outs, st, d, vp = self._sens_call(entry, JVP_OUTPUTS, shape, outs, status, stream, x)
+        tensors = ([getattr(self, k) for k in self._VJP_INPUTS] + [x, u, st] + [tangents.get(k) for k in self._JVP_TANGENTS]
+                   + [outs.get(k) for k in JVP_OUTPUTS])
+        _check(getattr(LIB, entry)(ctypes.byref(d), K, *[vp(t) for t in tensors],
+                                   ctypes.c_void_p(stream.cuda_stream)), entry)
+        return outs
+
+    def jvp_many_rows(self, outs, ntan=None):
+        """A jvp_many() result as numpy arrays: tx (batch, ntan, n), tu (batch, ntan, p + m), tf
+        (batch, ntan), whatever the layout.  ntan: by default what the tensors' second dimension
+        says (jvp_many() shapes them (rows, ntan * E))."""
+        per = {"tx": self.n, "tu": self.p + self.m, "tf": 1}
+        rows = {}
+        for k, t in outs.items():
+            K = int(ntan) if ntan is not None else t.shape[1] // max(per[k], 1)
+            rows[k] = self._rows(t, (K,) if k == "tf" else (K, per[k]))
+        return rows
+
     def kkt_rows(self, r):
         """A kkt_residuals() result as numpy (batch, 8), whatever the layout."""
         return self._rows(r, (KKT_NRES,))
@@ -1065,7 +1111,37 @@ def jvp(pr, x, u, tangents, status=None, layout=None, device="cuda:0", outs=None
     return db.jvp_rows(res)
 
 
-def _qp_jvp(box, G, g0, CE, ce0, c5, c6, tangents):
+def jvp_many(pr, x, u, tangents, status=None, layout=None, device="cuda:0", outs=None, ntan=None):
+    """jvp() along K directions per QP in one launch (qpgpu_jvp_many / qpgpu_jvp_box_many): every
+    tangent is shaped (B, K, ...), the result is tx (B, K, n), tu (B, K, p + m) and tf (B, K), and
+    direction k has the bits of jvp() on slice k.  ntan: K, by default the tangents' second dimension
+    (required when no tangent is given)."""
+    import torch
+
+    given = {k: np.asarray(t, dtype=np.float64) for k, t in tangents.items() if t is not None}
+    if ntan is None:
+        if not given:
+            raise ValueError("jvp_many without a tangent needs ntan")
+        ntan = next(iter(given.values())).shape[1]
+    K = int(ntan)
+    for k, t in given.items():
+        if t.ndim < 2 or t.shape[1] != K:
+            raise ValueError(f"the tangent of {k} is not (B, {K}, ...)")
+    db = (DeviceBoxBatch if isinstance(pr, BoxProblems) else DeviceBatch)(pr, device, with_iters=False, layout=layout)
+    B, E = pr.batch, pr.p + pr.m
+    conv = to_tiled64 if db.layout == LAYOUT_TILED64 else (lambda a: a)
+    up = lambda a, cols: torch.from_numpy(np.array(
+        conv(np.asarray(a, dtype=np.float64).reshape(B, cols)), dtype=np.float64, order="C")).to(device)
+    xd = up(x, pr.n)
+    ud = up(u, E) if E > 0 else None
+    sd = None if status is None else torch.from_numpy(np.array(status, dtype=np.int32, order="C")).to(device)
+    td = {k: up(t, t.size // B) for k, t in given.items() if t.size}
+    res = db.jvp_many(ud, td, K, outs=None if outs is None else dict.fromkeys(outs, True), status=sd, x=xd)
+    torch.cuda.synchronize(xd.device)
+    return db.jvp_many_rows(res, K)
+
+
+def _qp_jvp(box, G, g0, CE, ce0, c5, c6, tangents, many=False):
     import torch
 
     B, n, p = G.shape[0], G.shape[-1], CE.shape[-1]
@@ -1079,25 +1155,33 @@ def _qp_jvp(box, G, g0, CE, ce0, c5, c6, tangents):
             raise ValueError(f"{k!r} is no input of the QP: {names}")
     ins = [t.detach().contiguous() for t in (G, g0, CE, ce0, c5, c6)]
     tan = [None if tangents.get(k) is None else tangents[k].detach().contiguous() for k in names]
+    K = None
+    if many:
+        given = [t for t in tan if t is not None]
+        if not given or given[0].dim() < 2:
+            raise ValueError("qp_jvp_many takes at least one tangent, shaped (B, K, ...)")
+        K = int(given[0].shape[1])
     for k, a, t in zip(names, ins, tan):
-        if t is not None and t.shape != a.shape:
-            raise ValueError(f"the tangent of {k} has shape {tuple(t.shape)}, not {tuple(a.shape)}")
+        want = a.shape if K is None else a.shape[:1] + (K,) + a.shape[1:]
+        if t is not None and t.shape != want:
+            raise ValueError(f"the tangent of {k} has shape {tuple(t.shape)}, not {tuple(want)}")
     dev = G.device
     x = torch.zeros((B, n), dtype=torch.float64, device=dev)
     f = torch.empty(B, dtype=torch.float64, device=dev)
     st = torch.empty(B, dtype=torch.int32, device=dev)
     u = torch.zeros((B, p + m), dtype=torch.float64, device=dev)
-    tx = torch.empty((B, n), dtype=torch.float64, device=dev)
-    tu = torch.empty((B, p + m), dtype=torch.float64, device=dev)
-    tf = torch.empty(B, dtype=torch.float64, device=dev)
+    kdim = () if K is None else (K,)
+    tx = torch.empty((B,) + kdim + (n,), dtype=torch.float64, device=dev)
+    tu = torch.empty((B,) + kdim + (p + m,), dtype=torch.float64, device=dev)
+    tf = torch.empty((B,) + kdim, dtype=torch.float64, device=dev)
     d = ProblemDesc(n, p, m, 0, B, 0, LAYOUT_QP_MAJOR)
     vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     entry = "qpgpu_solve_batched_box_dual" if box else "qpgpu_solve_batched_dual"
     _check(getattr(LIB, entry)(ctypes.byref(d), *[vp(t) for t in ins], vp(x), vp(f), vp(st), None, vp(u), None,
                                stream), entry)
-    entry = "qpgpu_jvp_box" if box else "qpgpu_jvp"
-    data = (vp(ins[0]), vp(ins[2])) + (() if box else (vp(ins[4]),))
+    entry = ("qpgpu_jvp_box" if box else "qpgpu_jvp") + ("" if K is None else "_many")
+    data = (() if K is None else (K,)) + (vp(ins[0]), vp(ins[2])) + (() if box else (vp(ins[4]),))
     _check(getattr(LIB, entry)(ctypes.byref(d), *data, vp(x), vp(u), vp(st), *[vp(t) for t in tan], vp(tx), vp(tu),
                                vp(tf), stream), entry)
     return x, u, f, st, tx, tu, tf
@@ -1117,6 +1201,20 @@ def qp_jvp_box(G, g0, CE, ce0, hi, lo, tangents):
     """qp_jvp for bounds lo <= x <= hi (tangent names G, g0, CE, ce0, hi, lo): u and tu are
     (B, p + 2n), equalities, upper bounds, lower bounds (qpgpu_solve_batched_box_dual, then qpgpu_jvp_box)."""
     return _qp_jvp(True, G, g0, CE, ce0, hi, lo, tangents)
+
+
+def qp_jvp_many(G, g0, CE, ce0, CI, ci0, tangents):
+    """qp_jvp along K directions per QP: every tangent is shaped (B, K, ...) (at least one is given; a
+    missing name: a zero tangent in all K directions).  A dual solve, then qpgpu_jvp_many, on the
+    current stream: (x, u, f, status, tx, tu, tf) with tx (B, K, n), tu (B, K, p + m) and tf (B, K);
+    direction k has the bits of qp_jvp on slice k."""
+    return _qp_jvp(False, G, g0, CE, ce0, CI, ci0, tangents, many=True)
+
+
+def qp_jvp_box_many(G, g0, CE, ce0, hi, lo, tangents):
+    """qp_jvp_many for bounds lo <= x <= hi (tangent names G, g0, CE, ce0, hi, lo), as qp_jvp_box is
+    to qp_jvp (qpgpu_solve_batched_box_dual, then qpgpu_jvp_box_many)."""
+    return _qp_jvp(True, G, g0, CE, ce0, hi, lo, tangents, many=True)
 
 
 @functools.lru_cache(maxsize=None)
