@@ -455,16 +455,20 @@ __device__ __forceinline__ void qp_stamp(const QpArgs& a, int slot) {
 
 }  // namespace qpk
 
+// The lane family's size classes (n <= N, m <= M), smallest first; a shape runs in the first that
+// holds it.  The one list: every build's launcher (qp_lane.hip) and the kernel names (qpgpu_api.cpp
+// lane_name) are generated from it, so a new class is one more X(N, M) here.
+#define QPK_LANE_SIZES(X) X(7, 14) X(8, 16)
+
 // ---- what each kernel family exports to qpgpu_api.cpp (the library's internal boundary) ---------
 // One query and one launch per family and build.  *_name: the kernel the family runs for (n, m)
-// in `mode` (a qpk::Mode), NULL where it has none; no family's choice reads p.  qpk_launch_*:
-// enqueue that kernel for *a in mode_of(*a); the caller has asked *_name first, so a shape or
-// mode the build lacks is hipErrorInvalidValue, never a silent success.
+// in `mode` (a qpk::Mode), NULL where it has none; no family's choice reads p.  The lane family's
+// names are a host table over QPK_LANE_SIZES (qpgpu_api.cpp lane_name).  qpk_launch_*: enqueue that
+// kernel for *a in mode_of(*a); the caller has asked for the name first, so a shape or mode the
+// build lacks is hipErrorInvalidValue, never a silent success.
 extern "C" {
-const char* qpk_lane_name(int n, int m, int mode);       // qp_lane.hip, the exact build
-const char* qpk_lane_name_fast(int n, int m, int mode);  // ... with QPGPU_LANE_FAST
-hipError_t qpk_launch_lane(const qpk::QpArgs* a, hipStream_t stream);
-hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream);
+hipError_t qpk_launch_lane(const qpk::QpArgs* a, hipStream_t stream);  // qp_lane.hip, the exact build
+hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream);  // ... with QPGPU_LANE_FAST
 // the QPGPU_LANE_UNALIGNED builds of the two, launched when kArgStage16 is not set
 hipError_t qpk_launch_lane_u(const qpk::QpArgs* a, hipStream_t stream);
 hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream);
@@ -482,7 +486,6 @@ hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream);
 // The unit-Hessian builds (qpgpu_solve_batched_unit: G = I stated, a->G never read; plain mode
 // only, so no mode argument): qp_lane_unit.hip / qp_lane_unit_u.hip, qp_small.hip's fifth kernel,
 // qp_wave_unit.hip (the LDS variants).  A name is NULL where the family's unit build lacks the shape.
-const char* qpk_lane_name_unit(int n, int m);
 hipError_t qpk_launch_lane_unit(const qpk::QpArgs* a, hipStream_t stream);
 hipError_t qpk_launch_lane_unit_u(const qpk::QpArgs* a, hipStream_t stream);  // kArgStage16 not set
 const char* qpk_small_name_unit(int n, int m);

@@ -29,6 +29,14 @@
 // (Cholesky columns, J = L^-T, the solve, the Givens coefficients), and the rotation length as
 // sqrt(a^2 + b^2) for operands well inside the exponent range — within north_star's 1e-10
 // relative of the reference instead of bit-identical.
+//
+// Seven objects are built from this source: qp_lane.o and qp_lane_p0.o (the exact aligned build in
+// two parts), qp_lane_fast.o, the unaligned twins qp_lane_u.o and qp_lane_fast_u.o, and the unit-
+// Hessian qp_lane_unit.o and qp_lane_unit_u.o.  Their wrapper sources set the macros below, which
+// choose the namespace, the kernel's name, the entry's suffix and the branches inside lane_body.
+// What an object holds beyond that is a few constexpr facts beside kFast; the one launcher at the
+// end of the file selects on them, over the size classes of QPK_LANE_SIZES (qp_common.h), and the
+// kernel names are a host table over the same list (qpgpu_api.cpp lane_name).  DESIGN §5.14.
 #include <type_traits>
 #include <utility>
 
@@ -60,7 +68,25 @@
 #if QPGPU_LANE_UNIT && QPGPU_LANE_FAST
 #error "the unit-Hessian lane kernels restate the reference's operation order only"
 #endif
-#if QPGPU_LANE_UNIT && QPGPU_LANE_UNALIGNED
+// The exact aligned build is two objects: its p = 0 instantiations (C2, the joint-limit QPs) are
+// compiled in qp_lane_p0.hip (QPGPU_LANE_PART = 2) under LLVM's iterative-minreg scheduler, the
+// rest in qp_lane.o (QPGPU_LANE_PART = 1, Makefile DEFS_qp_lane) under iterative-ilp: measured C2
+// 71.2-71.9 -> 68.6-69.1 us with minreg, while C1 is slower with it (43.7-44.7 -> 46.1-47.9 us;
+// profiles/r05_s11).  Part 1's launcher forwards p = 0 to part 2's entry, qpk_launch_lane_p0.
+// Part 0 (every other build, A/B builds) keeps all of its instantiations in one object.
+#ifndef QPGPU_LANE_PART
+#define QPGPU_LANE_PART 0
+#endif
+#if QPGPU_LANE_PART && (QPGPU_LANE_FAST || QPGPU_LANE_UNALIGNED || QPGPU_LANE_UNIT)
+#error "only the exact aligned build is split into parts"
+#endif
+// The preprocessor's share of a build: the namespace, the kernel's name and the suffix of the
+// exported entry.  Everything else a build is or lacks is a constexpr fact below (kPart ...).
+#if QPGPU_LANE_PART == 2
+#define QPK_LANE_NS qpk
+#define QP_LANE_KERNEL qp_lane_kernel
+#define QPK_LANE_C(name) name##_p0
+#elif QPGPU_LANE_UNIT && QPGPU_LANE_UNALIGNED
 #define QPK_LANE_NS qpk_unit_u
 #define QP_LANE_KERNEL qp_lane_unit_kernel
 #define QPK_LANE_C(name) name##_unit_u
@@ -98,9 +124,26 @@
 #error "retired build switch: its default is folded into qp_lane.hip; the other side is an earlier revision (DESIGN 5.15, tools/ab_build.sh SRCFILE=)"
 #endif
 
+// part 2's entry, which part 1's launcher calls (between the two objects only, so declared here)
+extern "C" hipError_t qpk_launch_lane_p0(const qpk::QpArgs* a, hipStream_t stream);
+
 namespace QPK_LANE_NS {
 using namespace qpk;
 constexpr bool kFast = QPGPU_LANE_FAST != 0;
+// What this object holds, for the launcher at the end of the file (lane_body reads the macros):
+constexpr bool kUnit = QPGPU_LANE_UNIT != 0;
+constexpr int kPart = QPGPU_LANE_PART;
+// the compile-time-shape instantiations <EXACT = true>; the unit builds have the run-time shape only
+constexpr bool kFixedShapes = !kUnit;
+// the dual, box and box-dual kernels: the exact builds', with part 1 where the build is split
+constexpr bool kHasModes = !kFast && !kUnit && kPart != 2;
+// the full-wave kernels of (7, p, 14), p = 6 and p = 0: the exact aligned build's
+constexpr bool kHasFull = !kFast && !kUnit && QPGPU_LANE_UNALIGNED == 0;
+// the plain kernel <EXACT, PX>: part 2 holds <true, 0> and nothing else, part 1 all but that one
+constexpr bool has_plain(bool exact, int px) {
+  const bool p0 = exact && px == 0;
+  return (!exact || kFixedShapes) && (kPart == 0 || (kPart == 2) == p0);
+}
 constexpr bool kStamps = QPGPU_LANE_STAMPS != 0;
 __device__ __forceinline__ void lstamp(const QpArgs& a, int slot) {
   if constexpr (kStamps) qp_stamp(a, slot);
@@ -1821,261 +1864,133 @@ __global__ void __launch_bounds__(64, kLaneOcc) QP_LANE_KERNEL(const QpArgs a) {
   }
 }
 
-#if QPGPU_LANE_UNIT
-// The unit build's launch: the run-time-shape instantiation of each size class in both layouts
-// (EXACT = false, PX = -1: the ones that carry the m = 0 snapshot), nothing else.
-template <int NM, int MM>
-static hipError_t launch_lane_unit(const QpArgs& a, hipStream_t stream) {
-  const dim3 g((unsigned)((a.batch + kQpw - 1) / kQpw)), blk(64);
-  if (a.tile == 64)
-    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, 64, false, -1>), g, blk, 0, stream, a);
-  else
-    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, 1, false, -1>), g, blk, 0, stream, a);
-  return hipGetLastError();
-}
-}  // namespace QPK_LANE_NS
-
-extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream) {
-  if (a->u || a->hi) return hipErrorInvalidValue;  // no dual or box form
-  if (a->n <= 7 && a->m <= 14) return QPK_LANE_NS::launch_lane_unit<7, 14>(*a, stream);
-  if (a->n <= 8 && a->m <= 16) return QPK_LANE_NS::launch_lane_unit<8, 16>(*a, stream);
-  return hipErrorInvalidValue;
-}
-#if !QPGPU_LANE_UNALIGNED  // the unaligned build runs what its aligned twin names
-extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m) {
-  if (n <= 7 && m <= 14) return "qp_lane_unit<N=7,M=14>";
-  if (n <= 8 && m <= 16) return "qp_lane_unit<N=8,M=16>";
-  return nullptr;
-}
-#endif
-#else  // QPGPU_LANE_UNIT
-
-// The full-wave aligned kernels (lane_body's FULL) of the exact aligned build: the shapes behind
-// C1 / C4 (7, 6, 14) and C2 (7, 0, 14), in both layouts.  Kernels of their own, not a branch in the
-// kernels above (which stay the code they were; a branch in the kernel once pushed the N = 8
-// instantiations into scratch, profiles/placement/kernel_regs_branch_in_kernel.txt).
-#if !QPGPU_LANE_FAST && !QPGPU_LANE_UNALIGNED
-#define QPK_LANE_HAS_FULL 1
-template <int NM, int MM, int T, int PX>
-__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_full_kernel(const QpArgs a) {
-  __shared__ double sbuf[kStage];
-  lane_body<NM, MM, T, true, PX, true, false, false, true>(a, (LdsD*)sbuf);
-}
-// Does the full-wave kernel exist for this instantiation, and has the host established what it
-// assumes of the launch (apart from the whole waves, which launch_full_then_rest provides)?
-template <int NM, int MM>
-static bool full_wave_launch(const QpArgs& a) {
-  constexpr uint32_t kAligned = kArgStage16 | kArgAligned16;
-  return NM == 7 && MM == 14 && (a.flags & kAligned) == kAligned && !(a.flags & QPGPU_FLAG_WRITE_FACTOR) &&
-         !a.iters;
-}
-#else
-#define QPK_LANE_HAS_FULL 0
-template <int NM, int MM>
-static bool full_wave_launch(const QpArgs&) {
-  return false;
-}
-#endif
-// The whole 64-QP blocks of the batch through `full`, the remaining QPs (batch % 64) through
-// `rest` as a second launch on the same stream over the sub-range past those blocks.  A whole
-// number of 64-QP blocks is a whole number of tiles and of 512-byte steps, so the remainder's
-// arrays keep the layout and the 16-byte residues the host checked.
-template <class Full, class Rest>
-static void launch_full_then_rest(const QpArgs& a, Full&& full, Rest&& rest) {
-  const int64_t nb = a.batch / kQpw, done = nb * kQpw;
-  if (nb > 0) {
-    QpArgs c = a;
-    c.batch = done;
-    full(c, dim3((unsigned)nb));
-    qpk_lane_count_launch(1);
-  }
-  if (a.batch > done) {
-    QpArgs c = sub_range(a, done, a.batch - done);
-    c.stamps = a.stamps ? a.stamps + nb * kStampSlots : nullptr;  // (per wave, not per QP)
-    rest(c, dim3(1));
-    qpk_lane_count_launch(0);
-  }
-}
-
-// The exact build's p = 0 instantiations (C2, the joint-limit QPs) are compiled in their own
-// translation unit (qp_lane_p0.hip, QPGPU_LANE_PART = 2) under LLVM's iterative-minreg scheduler,
-// the rest (QPGPU_LANE_PART = 1) under iterative-ilp: measured C2 71.2-71.9 -> 68.6-69.1 us with
-// minreg, while C1 is slower with it (43.7-44.7 -> 46.1-47.9 us; profiles/r05_s11).  Part 0 (the
-// fast build, A/B builds) keeps every instantiation in one TU.
-#ifndef QPGPU_LANE_PART
-#define QPGPU_LANE_PART 0
-#endif
-#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
+// The kernels of the other modes and the full-wave kernels.  Templates, so an object that never
+// launches one (the facts at the top of the file) has no code for it.  Kernels of their own, not
+// branches in the kernel above, which stays the same code as without them: a branch in the kernel
+// once pushed the N = 8 instantiations into scratch
+// (profiles/placement/kernel_regs_branch_in_kernel.txt).
 // qpgpu_solve_batched_dual: the general instantiation (run-time n, p, m) carrying r and u over the
-// whole active set.  A kernel of its own, so the kernels above are the same code as without it.
+// whole active set.
 template <int NM, int MM, int T>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_dual_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
   lane_body<NM, MM, T, false, -1, true, true>(a, (LdsD*)sbuf);
 }
-// qpgpu_solve_batched_box: bounds instead of CI.  Kernels of their own: the compile-time p = 0
-// form of the exact shape (EXACT, PX = 0) and the run-time-shape form (any p, n <= NM).
+// qpgpu_solve_batched_box: bounds instead of CI.  The compile-time p = 0 form of the exact shape
+// (EXACT, PX = 0) and the run-time-shape form (any p, n <= NM).
 template <int NM, int MM, int T, bool EXACT, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
   lane_body<NM, MM, T, EXACT, PX, true, false, true>(a, (LdsD*)sbuf);
 }
 // qpgpu_solve_batched_box_dual: the two box forms with the multipliers carried and returned.
-// Kernels of their own again, so the box and dual kernels above are the same code as without them.
 template <int NM, int MM, int T, bool EXACT, int PX>
 __global__ void __launch_bounds__(64, kLaneOcc) qp_lane_box_dual_kernel(const QpArgs a) {
   __shared__ double sbuf[kStage];
   lane_body<NM, MM, T, EXACT, PX, true, true, true>(a, (LdsD*)sbuf);
 }
-#endif
-template <int NM, int MM, int T>
-static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream);
-template <int NM, int MM, int T>
-static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
-  const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
-  const dim3 g((unsigned)blocks), blk(64);
-  // the three other modes run kernels that only the exact build's part 0 / 1 has: elsewhere an error
-  switch (mode_of(a)) {
-#if !QPGPU_LANE_FAST && QPGPU_LANE_PART != 2
-    case kBoxDual:
-    case kBox:
-      if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
-      if (a.u) {
-        if (a.n == NM && a.p == 0)
-          hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
-        else
-          hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
-      } else if (a.n == NM && a.p == 0) {
-        hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
-      } else {
-        hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
-      }
-      return hipSuccess;
-    case kDual:
-      hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
-      return hipSuccess;
-#else
-    case kBoxDual:
-    case kBox:
-    case kDual:
-      return hipErrorInvalidValue;
-#endif
-    case kPlain:
-      break;
-  }
-  if (a.n == NM && a.m == MM && !a.x_eq) {
-#if QPK_LANE_HAS_FULL
-    if constexpr (NM == 7 && MM == 14)
-      if (a.p == 6 && full_wave_launch<NM, MM>(a)) {
-        launch_full_then_rest(
-            a,
-            [&](const QpArgs& c, dim3 gc) {
-              hipLaunchKernelGGL((qp_lane_full_kernel<NM, MM, T, 6>), gc, blk, 0, stream, c);
-            },
-            [&](const QpArgs& c, dim3 gc) {
-              hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 6>), gc, blk, 0, stream, c);
-            });
+// The full-wave aligned kernels (lane_body's FULL): the shapes behind C1 / C4 (7, 6, 14) and C2
+// (7, 0, 14), in both layouts.
+template <int NM, int MM, int T, int PX>
+__global__ void __launch_bounds__(64, kLaneOcc) qp_lane_full_kernel(const QpArgs a) {
+  __shared__ double sbuf[kStage];
+  lane_body<NM, MM, T, true, PX, true, false, false, true>(a, (LdsD*)sbuf);
+}
+
+// ---- the launcher: one policy for every build, read top to bottom ---------------------------------
+// qpk_launch_lane* (at the end) picks the size class, launch_lane_t the mode and the instantiation,
+// launch_plain enqueues a plain-mode kernel.  A kernel the object lacks is hipErrorInvalidValue.
+
+// The plain kernel <EXACT, PX> over the whole batch.
+template <int NM, int MM, int T, bool EXACT, int PX>
+static hipError_t launch_plain(const QpArgs& a, hipStream_t stream) {
+  if constexpr (kPart == 1 && EXACT && PX == 0) {
+    return qpk_launch_lane_p0(&a, stream);  // part 2 has these kernels (and their full-wave forms)
+  } else if constexpr (!has_plain(EXACT, PX)) {
+    return hipErrorInvalidValue;
+  } else {
+    const dim3 blk(64);
+    if constexpr (kHasFull && NM == 7 && MM == 14 && EXACT && PX >= 0) {
+      // What the full-wave kernel assumes of a launch, apart from whole waves: the LDS-DMA and
+      // double2 alignment bits, no factor written back, no iteration counts.
+      constexpr uint32_t kAligned = kArgStage16 | kArgAligned16;
+      if ((a.flags & kAligned) == kAligned && !(a.flags & QPGPU_FLAG_WRITE_FACTOR) && !a.iters) {
+        // The whole 64-QP blocks of the batch through it, the remaining QPs (batch % 64) through
+        // the general kernel as a second launch on the same stream over the sub-range past those
+        // blocks.  A whole number of 64-QP blocks is a whole number of tiles and of 512-byte
+        // steps, so the remainder's arrays keep the layout and the 16-byte residues the host
+        // checked.
+        const int64_t nb = a.batch / kQpw, done = nb * kQpw;
+        if (nb > 0) {
+          QpArgs c = a;
+          c.batch = done;
+          hipLaunchKernelGGL((qp_lane_full_kernel<NM, MM, T, PX>), dim3((unsigned)nb), blk, 0, stream, c);
+          qpk_lane_count_launch(1);
+        }
+        if (a.batch > done) {
+          QpArgs c = sub_range(a, done, a.batch - done);
+          c.stamps = a.stamps ? a.stamps + nb * kStampSlots : nullptr;  // (per wave, not per QP)
+          hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, PX>), dim3(1), blk, 0, stream, c);
+          qpk_lane_count_launch(0);
+        }
         return hipSuccess;
       }
-#endif
-    if (a.p == 6)
-      hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 6>), g, blk, 0, stream, a);
-    else if (a.p == 0)
-      return launch_lane_p0<NM, MM, T>(a, stream);
-    else
-      hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, -1>), g, blk, 0, stream, a);
-  } else {
-    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+    }
+    const dim3 g((unsigned)((a.batch + kQpw - 1) / kQpw));
+    hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, EXACT, PX>), g, blk, 0, stream, a);
+    return hipSuccess;
   }
-  return hipSuccess;
 }
 
-#if QPGPU_LANE_PART == 1
-}  // namespace QPK_LANE_NS
-extern "C" hipError_t qpk_launch_lane_p0(const qpk::QpArgs* a, hipStream_t stream);  // qp_lane_p0.hip
-namespace QPK_LANE_NS {
 template <int NM, int MM, int T>
-static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream) {
-  return qpk_launch_lane_p0(&a, stream);
-}
-#else
-template <int NM, int MM, int T>
-static hipError_t launch_lane_p0(const QpArgs& a, hipStream_t stream) {
-#if QPK_LANE_HAS_FULL
-  if constexpr (NM == 7 && MM == 14)
-    if (full_wave_launch<NM, MM>(a)) {
-      launch_full_then_rest(
-          a,
-          [&](const QpArgs& c, dim3 gc) {
-            hipLaunchKernelGGL((qp_lane_full_kernel<NM, MM, T, 0>), gc, dim3(64), 0, stream, c);
-          },
-          [&](const QpArgs& c, dim3 gc) {
-            hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 0>), gc, dim3(64), 0, stream, c);
-          });
+static hipError_t launch_lane_t(const QpArgs& a, hipStream_t stream) {
+  const Mode mode = mode_of(a);
+  if (mode != kPlain) {
+    if constexpr (!kHasModes) {
+      return hipErrorInvalidValue;
+    } else {
+      const dim3 g((unsigned)((a.batch + kQpw - 1) / kQpw)), blk(64);
+      if (mode != kDual) {
+        if (a.m != 2 * a.n || a.x_eq) return hipErrorInvalidValue;
+        if (a.u) {
+          if (a.n == NM && a.p == 0)
+            hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+          else
+            hipLaunchKernelGGL((qp_lane_box_dual_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+        } else if (a.n == NM && a.p == 0) {
+          hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, true, 0>), g, blk, 0, stream, a);
+        } else {
+          hipLaunchKernelGGL((qp_lane_box_kernel<NM, MM, T, false, -1>), g, blk, 0, stream, a);
+        }
+      } else {
+        hipLaunchKernelGGL((qp_lane_dual_kernel<NM, MM, T>), g, blk, 0, stream, a);
+      }
       return hipSuccess;
     }
-#endif
-  const int64_t blocks = (a.batch + kQpw - 1) / kQpw;
-  hipLaunchKernelGGL((QP_LANE_KERNEL<NM, MM, T, true, 0>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-  return hipSuccess;
+  }
+  // plain mode: the class's own shape (and no x_eq snapshot) runs a compile-time-shape kernel
+  if (kFixedShapes && a.n == NM && a.m == MM && !a.x_eq) {
+    if (a.p == 6) return launch_plain<NM, MM, T, true, 6>(a, stream);
+    if (a.p == 0) return launch_plain<NM, MM, T, true, 0>(a, stream);
+    return launch_plain<NM, MM, T, true, -1>(a, stream);
+  }
+  return launch_plain<NM, MM, T, false, -1>(a, stream);
 }
-#endif
 
-#if QPGPU_LANE_PART != 2
 template <int NM, int MM>
 static hipError_t launch_lane(const QpArgs& a, hipStream_t stream) {
   const hipError_t e = a.tile == 64 ? launch_lane_t<NM, MM, 64>(a, stream) : launch_lane_t<NM, MM, 1>(a, stream);
-  if (e != hipSuccess) return e;
-  return hipGetLastError();
+  return e != hipSuccess ? e : hipGetLastError();
 }
-
-struct LaneVariant {
-  int nmax, mmax;
-  const char* name[4];  // by Mode; the fast build has the plain kernels only
-  hipError_t (*launch)(const QpArgs&, hipStream_t);
-};
-
-#if QPGPU_LANE_FAST
-#define QPK_LANE_NAMES(s) {"qp_lane_fast<" s ">", nullptr, nullptr, nullptr}
-#else
-#define QPK_LANE_NAMES(s) {"qp_lane<" s ">", "qp_lane_dual<" s ">", "qp_lane_box<" s ">", "qp_lane_box_dual<" s ">"}
-#endif
-static const LaneVariant kLaneVariants[] = {
-    {7, 14, QPK_LANE_NAMES("N=7,M=14"), launch_lane<7, 14>},
-    {8, 16, QPK_LANE_NAMES("N=8,M=16"), launch_lane<8, 16>},
-};
-
-const LaneVariant* pick_lane(int n, int m) {
-  for (const auto& v : kLaneVariants)
-    if (n <= v.nmax && m <= v.mmax) return &v;
-  return nullptr;
-}
-#endif  // QPGPU_LANE_PART != 2
 
 }  // namespace QPK_LANE_NS
 
-#if QPGPU_LANE_PART == 2
-// part 2: the exact p = 0 kernels only (the caller, part 1's launch_lane_t, has matched the
-// shape).  A shape part 1 forwards that this list lacks (a LaneVariant added to kLaneVariants
-// without an entry here) is an error, never a silent success with nothing written.
-extern "C" hipError_t qpk_launch_lane_p0(const qpk::QpArgs* a, hipStream_t stream) {
-  using namespace QPK_LANE_NS;
-  if (a->n == 7 && a->m == 14)
-    return a->tile == 64 ? launch_lane_p0<7, 14, 64>(*a, stream) : launch_lane_p0<7, 14, 1>(*a, stream);
-  if (a->n == 8 && a->m == 16)
-    return a->tile == 64 ? launch_lane_p0<8, 16, 64>(*a, stream) : launch_lane_p0<8, 16, 1>(*a, stream);
+// qpk_launch_lane, _fast, _u, _fast_u, _unit, _unit_u, and part 2's qpk_launch_lane_p0: the first
+// size class of QPK_LANE_SIZES (qp_common.h) that holds the shape.
+extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream) {
+#define QPK_LANE_TRY(N, M) \
+  if (a->n <= N && a->m <= M) return QPK_LANE_NS::launch_lane<N, M>(*a, stream);
+  QPK_LANE_SIZES(QPK_LANE_TRY)
+#undef QPK_LANE_TRY
   return hipErrorInvalidValue;
 }
-#else
-extern "C" hipError_t QPK_LANE_C(qpk_launch_lane)(const qpk::QpArgs* a, hipStream_t stream) {
-  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(a->n, a->m);
-  return v ? v->launch(*a, stream) : hipErrorInvalidValue;
-}
-#if !QPGPU_LANE_UNALIGNED  // an unaligned build runs what its aligned twin names
-extern "C" const char* QPK_LANE_C(qpk_lane_name)(int n, int m, int mode) {
-  const QPK_LANE_NS::LaneVariant* v = QPK_LANE_NS::pick_lane(n, m);
-  return v ? v->name[mode] : nullptr;
-}
-#endif
-#endif  // QPGPU_LANE_PART == 2
-#endif  // QPGPU_LANE_UNIT

@@ -158,6 +158,29 @@ struct Pick {
   const char* name = "";
 };
 
+// The lane family's kernel for (n, m) in `mode`, by build: one row per size class of
+// QPK_LANE_SIZES, NULL where the build has no kernel — the fast and the unit builds restate the
+// plain kernels only.  (An unaligned build runs what its aligned twin names.)
+enum LaneBuild { kLaneExact, kLaneFast, kLaneUnit };
+static const char* lane_name(int n, int m, qpk::Mode mode, LaneBuild build) {
+  static const struct {
+    int nmax, mmax;
+    const char* name[3][4];  // [LaneBuild][qpk::Mode]
+  } rows[] = {
+#define QPK_LANE_NAMES(s)                                                                        \
+  {{"qp_lane<" s ">", "qp_lane_dual<" s ">", "qp_lane_box<" s ">", "qp_lane_box_dual<" s ">"}, \
+   {"qp_lane_fast<" s ">"},                                                                    \
+   {"qp_lane_unit<" s ">"}}
+#define QPK_LANE_ROW(N, M) {N, M, QPK_LANE_NAMES("N=" #N ",M=" #M)},
+      QPK_LANE_SIZES(QPK_LANE_ROW)
+#undef QPK_LANE_ROW
+#undef QPK_LANE_NAMES
+  };
+  for (const auto& r : rows)
+    if (n <= r.nmax && m <= r.mmax) return r.name[build][mode];
+  return nullptr;
+}
+
 static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode) {
   if (!flags_valid(flags)) return {};
   // the fast builds restate the plain kernels only: the other modes refuse QPGPU_FLAG_FAST
@@ -176,7 +199,7 @@ static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode) {
   // wave build.
   const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
   const char* s;
-  if (may(QPGPU_FLAG_FORCE_LANE) && (s = fast ? qpk_lane_name_fast(n, m, mode) : qpk_lane_name(n, m, mode)))
+  if (may(QPGPU_FLAG_FORCE_LANE) && (s = lane_name(n, m, mode, fast ? kLaneFast : kLaneExact)))
     return {kLane, fast, s};
   if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name(n, m, mode)))
     return {kSmall, false, s};
@@ -200,7 +223,7 @@ static Pick select_kernel_unit(int n, int p, int m, uint32_t flags) {
   const uint32_t force = flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP | QPGPU_FLAG_FORCE_WAVE);
   const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
   const char* s;
-  if (may(QPGPU_FLAG_FORCE_LANE) && (s = qpk_lane_name_unit(n, m))) return {kLane, false, s};
+  if (may(QPGPU_FLAG_FORCE_LANE) && (s = lane_name(n, m, qpk::kPlain, kLaneUnit))) return {kLane, false, s};
   if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name_unit(n, m)))
     return {kSmall, false, s};
   if (may(QPGPU_FLAG_FORCE_WAVE) && (s = qpk_medium_name_unit(n, m))) return {kWave, false, s};

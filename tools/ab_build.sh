@@ -31,8 +31,12 @@ print-defs:
 	@echo $(DEFS_$(SRCNAME))
 MK
 )
-# the fast lane build is the same source with QPGPU_LANE_FAST (qp_lane_fast.hip) and contraction
-XF=""; case "$SRC" in qp_lane_fast|qp_lane_fast_u|qp_wave_fast) XF="-ffp-contract=fast";; esac
+# the in-tree build's contraction flag of the source (Makefile CONTRACT_<source>: the fast builds)
+XF=$(make -s -C "$PKG" --no-print-directory -f Makefile -f - print-contract SRCNAME=$SRC <<'MK'
+print-contract:
+	@echo $(CONTRACT_$(SRCNAME))
+MK
+)
 # every object the Makefile links into lib/libqpgpu.so (its prerequisites, from make's database)
 OBJS=$(make -s -C "$PKG" --no-print-directory -pqn lib/libqpgpu.so 2>/dev/null | sed -n 's/^lib\/libqpgpu\.so: //p')
 [ -n "$OBJS" ] || { echo "ab_build: no prerequisites of lib/libqpgpu.so in the Makefile" >&2; exit 1; }
