@@ -352,8 +352,8 @@ struct QpArgs {
 constexpr int kStampSlots = 18;
 
 // The mode of a launch (host side): which of a family's four kernels runs — the kernel bodies'
-// two compile-time booleans, bit 0 DUAL (a.u is set), bit 1 BOX (a.hi is set).  Indexes the name
-// tables of the families' variants; the selection itself is qpgpu_api.cpp select_kernel().
+// two compile-time booleans, bit 0 DUAL (a.u is set), bit 1 BOX (a.hi is set).  Indexes the names
+// of a size class (qpgpu_api.cpp kernel_name); the selection itself is select_kernel() there.
 enum Mode { kPlain = 0, kDual = 1, kBox = 2, kBoxDual = 3 };
 inline Mode mode_of(const QpArgs& a) { return Mode((a.u ? kDual : kPlain) | (a.hi ? kBox : kPlain)); }
 
@@ -457,15 +457,24 @@ __device__ __forceinline__ void qp_stamp(const QpArgs& a, int slot) {
 
 // The lane family's size classes (n <= N, m <= M), smallest first; a shape runs in the first that
 // holds it.  The one list: every build's launcher (qp_lane.hip) and the kernel names (qpgpu_api.cpp
-// lane_name) are generated from it, so a new class is one more X(N, M) here.
+// kernel_name) are generated from it, so a new class is one more X(N, M) here.
 #define QPK_LANE_SIZES(X) X(7, 14) X(8, 16)
+// The subgroup family's size classes (S lanes per QP, n <= N, m <= M), smallest first, likewise the
+// one list: the launch table of qp_small.hip, its unit kernel's included, and the names.
+#define QPK_SMALL_SIZES(X) X(8, 8, 16) X(8, 8, 32) X(16, 16, 32) X(16, 16, 64)
+// The wave family's size classes (S, N, M) with J and R in LDS, smallest first: the launch table of
+// all three builds of qp_wave.hip (exact, fast, unit) and the names.
+#define QPK_WAVE_LDS_SIZES(X) X(16, 16, 32) X(32, 32, 64) X(32, 32, 128) X(64, 64, 128) X(64, 64, 256)
+// ... and its workspace class (J and R in a global workspace, n > 64), which only the exact build
+// has; it follows the LDS classes, so its bounds are the family's (qpgpu_max_n, qpgpu_max_m).
+#define QPK_WAVE_WS_SIZE(X) X(256, 256, 1024)
 
 // ---- what each kernel family exports to qpgpu_api.cpp (the library's internal boundary) ---------
-// One query and one launch per family and build.  *_name: the kernel the family runs for (n, m)
-// in `mode` (a qpk::Mode), NULL where it has none; no family's choice reads p.  The lane family's
-// names are a host table over QPK_LANE_SIZES (qpgpu_api.cpp lane_name).  qpk_launch_*: enqueue that
-// kernel for *a in mode_of(*a); the caller has asked for the name first, so a shape or mode the
-// build lacks is hipErrorInvalidValue, never a silent success.
+// One launch per family and build: qpk_launch_* enqueues the family's kernel for *a in mode_of(*a).
+// Which kernel that is, and whether the build has one for (n, m) and the mode, the host states once:
+// qpgpu_api.cpp kernel_name, a table over family, build and mode generated from the size lists
+// above.  The caller has asked it first, so a shape or mode the build lacks is
+// hipErrorInvalidValue, never a silent success.  No family's choice reads p.
 extern "C" {
 hipError_t qpk_launch_lane(const qpk::QpArgs* a, hipStream_t stream);  // qp_lane.hip, the exact build
 hipError_t qpk_launch_lane_fast(const qpk::QpArgs* a, hipStream_t stream);  // ... with QPGPU_LANE_FAST
@@ -476,23 +485,17 @@ hipError_t qpk_launch_lane_fast_u(const qpk::QpArgs* a, hipStream_t stream);
 // 64-QP blocks (full = 1: the full-wave kernel was enqueued) and the remaining QPs (full = 0: the
 // general kernel for them): the counts behind the test hook qpgpu_debug_lane_launches
 void qpk_lane_count_launch(int full);
-const char* qpk_small_name(int n, int m, int mode);  // qp_small.hip
-hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream);
-const char* qpk_medium_name(int n, int m, int mode);       // qp_wave.hip
-const char* qpk_medium_name_fast(int n, int m, int mode);  // ... with QPGPU_WAVE_FAST (LDS variants)
+hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream);  // qp_small.hip
 int64_t qpk_medium_workspace_bytes(const qpk::QpArgs* a);  // device workspace of a launch (0 = none)
-hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream, double* ws);
-hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream);
+hipError_t qpk_launch_medium(const qpk::QpArgs* a, hipStream_t stream, double* ws);  // qp_wave.hip
+hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream);  // ... with QPGPU_WAVE_FAST (LDS classes)
 // The unit-Hessian builds (qpgpu_solve_batched_unit: G = I stated, a->G never read; plain mode
-// only, so no mode argument): qp_lane_unit.hip / qp_lane_unit_u.hip, qp_small.hip's fifth kernel,
-// qp_wave_unit.hip (the LDS variants).  A name is NULL where the family's unit build lacks the shape.
+// only): qp_lane_unit.hip / qp_lane_unit_u.hip, qp_small.hip's fifth kernel, qp_wave_unit.hip (the
+// LDS classes).
 hipError_t qpk_launch_lane_unit(const qpk::QpArgs* a, hipStream_t stream);
 hipError_t qpk_launch_lane_unit_u(const qpk::QpArgs* a, hipStream_t stream);  // kArgStage16 not set
-const char* qpk_small_name_unit(int n, int m);
 hipError_t qpk_launch_small_unit(const qpk::QpArgs* a, hipStream_t stream);
-const char* qpk_medium_name_unit(int n, int m);
 hipError_t qpk_launch_medium_unit(const qpk::QpArgs* a, hipStream_t stream);
-const char* qpk_generic_name(int n, int m, int mode);  // qp_generic.hip
-int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch);
+int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch);  // qp_generic.hip
 hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws);
 }

@@ -698,20 +698,8 @@ __global__ void __launch_bounds__(kGenBS) qp_generic_box_dual_kernel(const QpArg
 
 }  // namespace qpk
 
-// Largest shape the generic kernel accepts: n*n and the workspace offsets stay within int64 and a
-// QP's workspace within 2^34 doubles (128 GiB); int32 element indices of the inputs (n*n, n*m).
-// CE offsets (n*p, j*p + i) are computed in int64, so p is not bounded here.
-static bool generic_covers(int n, int m) {
-  return n >= 1 && m >= 0 && (int64_t)n * n < ((int64_t)1 << 31) && (int64_t)n * m < ((int64_t)1 << 31);
-}
 extern "C" int64_t qpk_generic_workspace_bytes(int n, int m, int64_t batch) {
   return qpk::gen_lay(n, m).per_qp * 8 * batch;
-}
-extern "C" const char* qpk_generic_name(int n, int m, int mode) {
-  static const char* const kNames[4] = {  // by Mode
-      "qp_generic<BS=256,global workspace>", "qp_generic_dual<BS=256,global workspace>",
-      "qp_generic_box<BS=256,global workspace>", "qp_generic_box_dual<BS=256,global workspace>"};
-  return generic_covers(n, m) ? kNames[mode] : nullptr;
 }
 extern "C" hipError_t qpk_launch_generic(const qpk::QpArgs* a, hipStream_t stream, double* ws) {
   if (a->batch <= 0) return hipSuccess;

@@ -36,7 +36,7 @@
 // choose the namespace, the kernel's name, the entry's suffix and the branches inside lane_body.
 // What an object holds beyond that is a few constexpr facts beside kFast; the one launcher at the
 // end of the file selects on them, over the size classes of QPK_LANE_SIZES (qp_common.h), and the
-// kernel names are a host table over the same list (qpgpu_api.cpp lane_name).  DESIGN §5.14.
+// kernel names are a host table over the same list (qpgpu_api.cpp kernel_name).  DESIGN §5.14.
 #include <type_traits>
 #include <utility>
 

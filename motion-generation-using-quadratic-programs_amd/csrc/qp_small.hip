@@ -114,90 +114,63 @@ struct SmallCfg {
 // ------------------------------------------------------------------------------------------
 // launch table
 // ------------------------------------------------------------------------------------------
-template <int S, int NM, int MM>
+// One launcher per size class: its kernel for mode_of(a), or (UNIT) its unit-Hessian kernel, which
+// has no dual or box form.
+template <int S, int NM, int MM, bool UNIT>
 static hipError_t launch_small(const QpArgs& a, hipStream_t stream) {
   using C = SmallCfg<S, NM, MM>;
   const dim3 g((unsigned)((a.batch + C::QPW - 1) / C::QPW)), blk(64);
-  switch (mode_of(a)) {
-    case kBoxDual:
-      hipLaunchKernelGGL((qp_small_box_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
-      break;
-    case kBox:
-      hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), g, blk, 0, stream, a);
-      break;
-    case kDual:
-      hipLaunchKernelGGL((qp_small_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
-      break;
-    case kPlain:
-      hipLaunchKernelGGL((qp_small_kernel<S, NM, MM>), g, blk, 0, stream, a);
-      break;
+  const Mode mode = mode_of(a);
+  if constexpr (UNIT) {
+    if (mode != kPlain) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((qp_small_unit_kernel<S, NM, MM>), g, blk, 0, stream, a);
+  } else {
+    switch (mode) {
+      case kBoxDual:
+        hipLaunchKernelGGL((qp_small_box_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
+        break;
+      case kBox:
+        hipLaunchKernelGGL((qp_small_box_kernel<S, NM, MM>), g, blk, 0, stream, a);
+        break;
+      case kDual:
+        hipLaunchKernelGGL((qp_small_dual_kernel<S, NM, MM>), g, blk, 0, stream, a);
+        break;
+      case kPlain:
+        hipLaunchKernelGGL((qp_small_kernel<S, NM, MM>), g, blk, 0, stream, a);
+        break;
+    }
   }
   return hipGetLastError();
 }
 
+// The size classes of QPK_SMALL_SIZES (qp_common.h), once for the four kernels by mode and once
+// for the unit kernel; the names are the host's table over the same list (qpgpu_api.cpp kernel_name).
 struct SmallVariant {
   int nmax, mmax;
-  const char* name[4];  // by Mode
   hipError_t (*launch)(const QpArgs&, hipStream_t);
 };
-
-#define QPK_SMALL_NAMES(s) {"qp_small<" s ">", "qp_small_dual<" s ">", "qp_small_box<" s ">", "qp_small_box_dual<" s ">"}
-static const SmallVariant kSmallVariants[] = {
-    {8, 16, QPK_SMALL_NAMES("S=8,N=8,M=16"), launch_small<8, 8, 16>},
-    {8, 32, QPK_SMALL_NAMES("S=8,N=8,M=32"), launch_small<8, 8, 32>},
-    {16, 32, QPK_SMALL_NAMES("S=16,N=16,M=32"), launch_small<16, 16, 32>},
-    {16, 64, QPK_SMALL_NAMES("S=16,N=16,M=64"), launch_small<16, 16, 64>},
+#define QPK_SMALL_COUNT(S, N, M) +1
+static const SmallVariant kSmallVariants[2][QPK_SMALL_SIZES(QPK_SMALL_COUNT)] = {  // [unit][class]
+#define QPK_SMALL_ROW(S, N, M) {N, M, launch_small<S, N, M, false>},
+#define QPK_SMALL_UNIT_ROW(S, N, M) {N, M, launch_small<S, N, M, true>},
+    {QPK_SMALL_SIZES(QPK_SMALL_ROW)}, {QPK_SMALL_SIZES(QPK_SMALL_UNIT_ROW)}
+#undef QPK_SMALL_ROW
+#undef QPK_SMALL_UNIT_ROW
 };
+#undef QPK_SMALL_COUNT
 
-// the unit-Hessian kernel of each variant (no dual or box form)
-template <int S, int NM, int MM>
-static hipError_t launch_small_unit(const QpArgs& a, hipStream_t stream) {
-  using C = SmallCfg<S, NM, MM>;
-  const dim3 g((unsigned)((a.batch + C::QPW - 1) / C::QPW)), blk(64);
-  hipLaunchKernelGGL((qp_small_unit_kernel<S, NM, MM>), g, blk, 0, stream, a);
-  return hipGetLastError();
-}
-struct SmallUnitVariant {
-  int nmax, mmax;
-  const char* name;
-  hipError_t (*launch)(const QpArgs&, hipStream_t);
-};
-static const SmallUnitVariant kSmallUnitVariants[] = {
-    {8, 16, "qp_small_unit<S=8,N=8,M=16>", launch_small_unit<8, 8, 16>},
-    {8, 32, "qp_small_unit<S=8,N=8,M=32>", launch_small_unit<8, 8, 32>},
-    {16, 32, "qp_small_unit<S=16,N=16,M=32>", launch_small_unit<16, 16, 32>},
-    {16, 64, "qp_small_unit<S=16,N=16,M=64>", launch_small_unit<16, 16, 64>},
-};
-const SmallUnitVariant* pick_small_unit(int n, int m) {
-  for (const auto& v : kSmallUnitVariants)
-    if (n <= v.nmax && m <= v.mmax) return &v;
-  return nullptr;
-}
-
-const SmallVariant* pick_small(int n, int m) {
-  for (const auto& v : kSmallVariants)
-    if (n <= v.nmax && m <= v.mmax) return &v;  // any p: iq never exceeds n
-  return nullptr;
+// the first size class that holds the shape
+static hipError_t launch_small_class(const QpArgs& a, hipStream_t stream, bool unit) {
+  for (const auto& v : kSmallVariants[unit])
+    if (a.n <= v.nmax && a.m <= v.mmax) return v.launch(a, stream);  // any p: iq never exceeds n
+  return hipErrorInvalidValue;
 }
 
 }  // namespace qpk
 
 extern "C" hipError_t qpk_launch_small(const qpk::QpArgs* a, hipStream_t stream) {
-  const qpk::SmallVariant* v = qpk::pick_small(a->n, a->m);
-  return v ? v->launch(*a, stream) : hipErrorInvalidValue;
+  return qpk::launch_small_class(*a, stream, false);
 }
-
-extern "C" const char* qpk_small_name(int n, int m, int mode) {
-  const qpk::SmallVariant* v = qpk::pick_small(n, m);
-  return v ? v->name[mode] : nullptr;
-}
-
 extern "C" hipError_t qpk_launch_small_unit(const qpk::QpArgs* a, hipStream_t stream) {
-  const qpk::SmallUnitVariant* v = qpk::pick_small_unit(a->n, a->m);
-  return (v && !a->u && !a->hi) ? v->launch(*a, stream) : hipErrorInvalidValue;
-}
-
-extern "C" const char* qpk_small_name_unit(int n, int m) {
-  const qpk::SmallUnitVariant* v = qpk::pick_small_unit(n, m);
-  return v ? v->name : nullptr;
+  return qpk::launch_small_class(*a, stream, true);
 }

@@ -47,12 +47,18 @@
 #if QPGPU_WAVE_UNIT && QPGPU_WAVE_FAST
 #error "the unit-Hessian wave kernels restate the reference's operation order only"
 #endif
+// The preprocessor's share of a build: the namespace, the kernel's name and the suffix of the
+// exported entry (the exact build's entry, qpk_launch_medium, is written out at the end of the file
+// with the workspace class's sequencing).  What else a build is or lacks is a constexpr fact below
+// (kWaveUnit ...).
 #if QPGPU_WAVE_UNIT
 #define QPK_WAVE_NS qpk_wunit
 #define QP_WAVE_KERNEL qp_wave_unit_kernel
+#define QPK_WAVE_C(name) name##_unit
 #elif QPGPU_WAVE_FAST
 #define QPK_WAVE_NS qpk_wfast
 #define QP_WAVE_KERNEL qp_wave_fast_kernel
+#define QPK_WAVE_C(name) name##_fast
 #else
 #define QPK_WAVE_NS qpk
 #define QP_WAVE_KERNEL qp_wave_kernel
@@ -71,6 +77,12 @@
 namespace QPK_WAVE_NS {
 using namespace qpk;
 constexpr bool kWaveFast = QPGPU_WAVE_FAST != 0;
+// What this object holds, for the launcher at the end of the file (wave_body reads the macros):
+constexpr bool kWaveUnit = QPGPU_WAVE_UNIT != 0;
+// the dual, box and box-dual kernels: the exact build's
+constexpr bool kHasModes = !kWaveFast && !kWaveUnit;
+// the workspace class (QPK_WAVE_WS_SIZE: J and R in global memory): the exact build's
+constexpr bool kHasWs = !kWaveFast && !kWaveUnit;
 
 // ---- the fast build's arithmetic (F = kWaveFast and not the IEEE fallback body)
 // 1 / b: v_rcp_f64 + the two Newton steps of the compiler's own division sequence (without its
@@ -2550,7 +2562,8 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : OCC)
   }
 }
 
-#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
+// The kernels of the other modes.  Templates, so an object that never launches one (kHasModes at the
+// top of the file) has no code for it.
 // qpgpu_solve_batched_dual: a kernel of its own (one per variant, the OCC = 1 layout), so the
 // kernels above are the same code as without it
 template <int S, int NMAX, int MMAX, bool GJR>
@@ -2570,12 +2583,13 @@ __global__ void __launch_bounds__(S >= 64 ? S : 64, GJR ? kGjrOcc : 1)
     qp_wave_box_dual_kernel(const QpArgs a, double* __restrict__ ws) {
   wave_body<S, NMAX, MMAX, GJR, 1, false, true, true>(a, ws);
 }
-#endif
 
-// ------------------------------------------------------------------------------------------
+// ---- the launcher: one policy for every build, read top to bottom ---------------------------------
+// The entry (at the end) picks the size class, launch_wave the mode and the instantiation.  A
+// kernel the object lacks is hipErrorInvalidValue.
 using WaveKernel = void (*)(const QpArgs, double*);
 
-// Dynamic LDS beyond 64 KiB must be granted per kernel and device (callers test bytes > 65536
+// Dynamic LDS beyond 64 KiB must be granted per kernel and device (the caller tests bytes > 65536
 // first, so smaller launches never come here).  Host threads may launch concurrently
 // (include/qpgpu.h), so the record of what was granted is locked.
 static hipError_t grant_dynamic_lds(WaveKernel kernel, size_t bytes) {
@@ -2595,104 +2609,78 @@ static hipError_t grant_dynamic_lds(WaveKernel kernel, size_t bytes) {
   return hipSuccess;
 }
 
-#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
-// the dual, box and box-dual kernels: the OCC = 1 instantiation's layout, R packed where that one
-// sets up in registers
-template <int S, int NMAX, int MMAX, bool GJR>
-static hipError_t launch_wave_mode(WaveKernel kernel, const QpArgs& a, hipStream_t stream, double* ws) {
-  using C = WaveCfg<S, NMAX, MMAX, GJR>;
-  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  const bool rpack = S < 64 && !GJR;
-  const size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
-  if (lds_bytes > 65536) {
-    const hipError_t e = grant_dynamic_lds(kernel, lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(C::BS), lds_bytes, stream, a, ws);
-  return hipGetLastError();
-}
-#endif
-
 template <int S, int NMAX, int MMAX, bool GJR>
 static hipError_t launch_wave(const QpArgs& a, hipStream_t stream, double* ws) {
-  using C = WaveCfg<S, NMAX, MMAX, GJR>;
-  const int64_t blocks = (a.batch + C::QPB - 1) / C::QPB;
-  // the three other modes run kernels that only the exact build has: in the fast build an error
-  switch (mode_of(a)) {
-#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
-    case kBoxDual:
-      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
-    case kBox:
-      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_box_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
-    case kDual:
-      return launch_wave_mode<S, NMAX, MMAX, GJR>(qp_wave_dual_kernel<S, NMAX, MMAX, GJR>, a, stream, ws);
-#else
-    case kBoxDual:
-    case kBox:
-    case kDual:
-      return hipErrorInvalidValue;
-#endif
-    case kPlain:
-      break;
-  }
-  size_t lds_bytes = (size_t)C::QPB * wave_lay(a.n, a.m, GJR).stride * sizeof(double);
-  // Two-QP-per-wave variants: when a block's LDS leaves room for >= 2 waves per SIMD (<= 20 KiB,
-  // i.e. >= 8 one-wave blocks per CU) register pressure is the occupancy limit, so launch the
-  // instantiation compiled for 4 waves per SIMD (a few spilled VGPRs).  Measured: mgqp level 0
-  // (10.5 KiB per block) 2.44 -> 2.32 ms; C3 (37 KiB per block, LDS-limited to one wave per SIMD)
-  // keeps the unconstrained allocation (21.0 vs 22.0 ms).  The register-setup instantiations
-  // (OCC 2 for S = 16, OCC 1) use the packed-R layout.
-  if constexpr (S < 64 && !GJR) {
-    if (lds_bytes <= kOcc4Lds) {
-      hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, kOccSmall>), dim3((unsigned)blocks), dim3(C::BS),
-                         lds_bytes, stream, a, ws);
-      return hipGetLastError();
+  if constexpr (GJR && !kHasWs) {
+    return hipErrorInvalidValue;
+  } else {
+    using C = WaveCfg<S, NMAX, MMAX, GJR>;
+    const dim3 grid((unsigned)((a.batch + C::QPB - 1) / C::QPB)), blk(C::BS);
+    const auto lds_of = [&](bool rpack) {
+      return (size_t)C::QPB * wave_lay(a.n, a.m, GJR, rpack).stride * sizeof(double);
+    };
+    // The OCC = 1 instantiations' layout: R packed where they set up in registers.  The dual, box
+    // and box-dual kernels are OCC = 1 layouts, and so is the plain kernel of a launch that none of
+    // the two branches below takes.
+    const size_t lds_bytes = lds_of(S < 64 && !GJR);
+    WaveKernel kernel;
+    const Mode mode = mode_of(a);
+    if (mode != kPlain) {
+      if constexpr (!kHasModes) {
+        return hipErrorInvalidValue;
+      } else {
+        if (mode == kBoxDual)
+          kernel = qp_wave_box_dual_kernel<S, NMAX, MMAX, GJR>;
+        else if (mode == kBox)
+          kernel = qp_wave_box_kernel<S, NMAX, MMAX, GJR>;
+        else
+          kernel = qp_wave_dual_kernel<S, NMAX, MMAX, GJR>;
+      }
+    } else {
+      // Two-QP-per-wave variants: when a block's LDS leaves room for >= 2 waves per SIMD (<= 20 KiB,
+      // i.e. >= 8 one-wave blocks per CU) register pressure is the occupancy limit, so launch the
+      // instantiation compiled for 4 waves per SIMD (a few spilled VGPRs).  Measured: mgqp level 0
+      // (10.5 KiB per block) 2.44 -> 2.32 ms; C3 (37 KiB per block, LDS-limited to one wave per SIMD)
+      // keeps the unconstrained allocation (21.0 vs 22.0 ms).  The register-setup instantiations
+      // (OCC 2 for S = 16, OCC 1) use the packed-R layout.
+      if constexpr (S < 64 && !GJR) {
+        const size_t lds_full = lds_of(false);
+        if (lds_full <= kOcc4Lds) {
+          hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, kOccSmall>), grid, blk, lds_full, stream, a, ws);
+          return hipGetLastError();
+        }
+        // four-QP waves (S = 16): up to 40 KiB per block still leaves room for two waves per SIMD
+        if (S == 16 && lds_full <= 40960) {
+          hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, 2>), grid, blk, lds_bytes, stream, a, ws);
+          return hipGetLastError();
+        }
+      }
+      kernel = QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>;
     }
-    const size_t lds_p = (size_t)C::QPB * wave_lay(a.n, a.m, GJR, true).stride * sizeof(double);
-    // four-QP waves (S = 16): up to 40 KiB per block still leaves room for two waves per SIMD
-    if (S == 16 && lds_bytes <= 40960) {
-      hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR, 2>), dim3((unsigned)blocks), dim3(C::BS),
-                         lds_p, stream, a, ws);
-      return hipGetLastError();
+    if (lds_bytes > 65536) {
+      const hipError_t e = grant_dynamic_lds(kernel, lds_bytes);
+      if (e != hipSuccess) return e;
     }
-    lds_bytes = lds_p;  // OCC 1 (register setup) from here on
+    hipLaunchKernelGGL(kernel, grid, blk, lds_bytes, stream, a, ws);
+    return hipGetLastError();
   }
-  if (lds_bytes > 65536) {
-    const hipError_t e = grant_dynamic_lds(QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>, lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((QP_WAVE_KERNEL<S, NMAX, MMAX, GJR>), dim3((unsigned)blocks), dim3(C::BS), lds_bytes,
-                     stream, a, ws);
-  return hipGetLastError();
 }
 
+// The size classes of QPK_WAVE_LDS_SIZES and QPK_WAVE_WS_SIZE (qp_common.h); the names are the
+// host's table over the same lists (qpgpu_api.cpp kernel_name).  Every build lists the workspace
+// class; where kHasWs is false its launch is an error.  (Its plain mode's default is the panel
+// path, qpk_launch_medium below; the other modes always run EXACT, without it.)
 struct WaveVariant {
   int nmax, mmax;
   int64_t ws_doubles_per_qp;
-  const char* name[4];  // by Mode; the fast build has the plain kernels only
   hipError_t (*launch)(const QpArgs&, hipStream_t, double*);
 };
-
-#if QPGPU_WAVE_UNIT
-#define QPK_WAVE_NAMES(plain, s) {"qp_wave_unit<" s ">", nullptr, nullptr, nullptr}
-#elif QPGPU_WAVE_FAST
-#define QPK_WAVE_NAMES(plain, s) {"qp_wave_fast<" s ">", nullptr, nullptr, nullptr}
-#else
-#define QPK_WAVE_NAMES(plain, s) {plain "qp_wave<" s ">", "qp_wave_dual<" s ">", "qp_wave_box<" s ">", "qp_wave_box_dual<" s ">"}
-#endif
 static const WaveVariant kWaveVariants[] = {
-    // four QPs per wave (S = 16) for n <= 16, m <= 32 (the mgqp hierarchy levels)
-    {16, 32, 0, QPK_WAVE_NAMES("", "S=16,N=16,M=32"), launch_wave<16, 16, 32, false>},
-    {32, 64, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=64"), launch_wave<32, 32, 64, false>},
-    {32, 128, 0, QPK_WAVE_NAMES("", "S=32,N=32,M=128"), launch_wave<32, 32, 128, false>},
-    {64, 128, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=128"), launch_wave<64, 64, 128, false>},
-    {64, 256, 0, QPK_WAVE_NAMES("", "S=64,N=64,M=256"), launch_wave<64, 64, 256, false>},
-#if !QPGPU_WAVE_FAST && !QPGPU_WAVE_UNIT
-    // (the plain mode's default is the panel path; the other modes always run EXACT, without it)
-    {256, 1024, WaveCfg<256, 256, 1024, true>::WS_DOUBLES,
-     QPK_WAVE_NAMES("qp_panel<MFMA f64 16x16x4> + ", "S=256,N=256,M=1024,global J/R"),
-     launch_wave<256, 256, 1024, true>},
-#endif
+#define QPK_WAVE_ROW(S, N, M) {N, M, 0, launch_wave<S, N, M, false>},
+#define QPK_WAVE_WS_ROW(S, N, M) {N, M, WaveCfg<S, N, M, true>::WS_DOUBLES, launch_wave<S, N, M, true>},
+    QPK_WAVE_LDS_SIZES(QPK_WAVE_ROW) QPK_WAVE_WS_SIZE(QPK_WAVE_WS_ROW)
+#undef QPK_WAVE_ROW
+#undef QPK_WAVE_WS_ROW
 };
 
 const WaveVariant* pick_wave(int n, int m) {
@@ -2703,34 +2691,16 @@ const WaveVariant* pick_wave(int n, int m) {
 
 }  // namespace QPK_WAVE_NS
 
-#if QPGPU_WAVE_UNIT
-// the unit build covers the LDS variants only (n <= 64, m <= 256), in the plain mode
-extern "C" const char* qpk_medium_name_unit(int n, int m) {
-  const qpk_wunit::WaveVariant* v = qpk_wunit::pick_wave(n, m);
-  return v ? v->name[0] : nullptr;
-}
-extern "C" hipError_t qpk_launch_medium_unit(const qpk::QpArgs* a, hipStream_t stream) {
-  const qpk_wunit::WaveVariant* v = qpk_wunit::pick_wave(a->n, a->m);
-  return v ? v->launch(*a, stream, nullptr) : hipErrorInvalidValue;
-}
-#elif QPGPU_WAVE_FAST
-// the fast build covers the LDS variants only (n <= 64, m <= 256); wider shapes keep the
-// default path (its n > 64 form is already the 1e-10 tolerance mode)
-extern "C" const char* qpk_medium_name_fast(int n, int m, int mode) {
-  const qpk_wfast::WaveVariant* v = qpk_wfast::pick_wave(n, m);
-  return v ? v->name[mode] : nullptr;
-}
-extern "C" hipError_t qpk_launch_medium_fast(const qpk::QpArgs* a, hipStream_t stream) {
-  const qpk_wfast::WaveVariant* v = qpk_wfast::pick_wave(a->n, a->m);
+// What only the preprocessor can do for the host part: the exact build alone defines the library's
+// one copy of the workspace class's host code, a kernel that is not a template among it.
+#if QPGPU_WAVE_FAST || QPGPU_WAVE_UNIT
+// qpk_launch_medium_fast, qpk_launch_medium_unit: the LDS classes only (n <= 64, m <= 256), in the
+// plain mode; wider shapes keep the default path (its n > 64 form is already the 1e-10 tolerance mode)
+extern "C" hipError_t QPK_WAVE_C(qpk_launch_medium)(const qpk::QpArgs* a, hipStream_t stream) {
+  const QPK_WAVE_NS::WaveVariant* v = QPK_WAVE_NS::pick_wave(a->n, a->m);
   return v ? v->launch(*a, stream, nullptr) : hipErrorInvalidValue;
 }
 #else
-extern "C" const char* qpk_medium_name(int n, int m, int mode) {
-  const qpk::WaveVariant* v = qpk::pick_wave(n, m);
-  return v ? v->name[mode] : nullptr;
-}
-extern "C" int qpk_medium_max_n(void) { return 256; }
-extern "C" int qpk_medium_max_m(void) { return 1024; }
 extern "C" hipError_t qpk_launch_panel_setup(const qpk::QpArgs* a, hipStream_t stream, double* ws);
 
 // Workspace variants (n > 64) run the MFMA panel setup (qp_panel.hip) first unless the caller
@@ -2808,4 +2778,4 @@ extern "C" hipError_t qpk_shadow_stats(unsigned long long* out, int reset) {
   }
   return e;
 }
-#endif  // QPGPU_WAVE_FAST
+#endif  // QPGPU_WAVE_FAST || QPGPU_WAVE_UNIT

@@ -24,8 +24,6 @@
 #include "qp_jvp_many.h"
 #include "qp_vjp.h"
 
-extern "C" int qpk_medium_max_n(void);
-extern "C" int qpk_medium_max_m(void);
 extern "C" hipError_t qpk_relayout(int64_t batch, int E, const double* src, double* dst,
                                    int to_tiled, hipStream_t stream);
 
@@ -126,15 +124,13 @@ int qpgpu_device_count(void) {
   return c;
 }
 
-int qpgpu_max_n(void) {
-  int mn = qpk_medium_max_n();
-  return mn > 16 ? mn : 16;
-}
-
-int qpgpu_max_m(void) {
-  int mm = qpk_medium_max_m();
-  return mm > 64 ? mm : 64;
-}
+// the wave family's workspace class, the largest a table kernel holds (the generic kernel beyond it)
+#define QPK_CLASS_N(S, N, M) N
+#define QPK_CLASS_M(S, N, M) M
+int qpgpu_max_n(void) { return QPK_WAVE_WS_SIZE(QPK_CLASS_N); }
+int qpgpu_max_m(void) { return QPK_WAVE_WS_SIZE(QPK_CLASS_M); }
+#undef QPK_CLASS_N
+#undef QPK_CLASS_M
 
 // Default family order: lane (n <= 8, m <= 16), then the subgroup kernel only where it is the
 // faster one — n <= 8, m <= 32 (its S = 8 variants) — then the wave kernels.  Measured on MI355X
@@ -147,91 +143,107 @@ static bool default_small(int n, int m) { return n <= 8 && m <= 32; }
 // sub-batches (launch_generic).  4 GiB; qpgpu_debug_set_generic_ws_cap lowers it in tests.
 static int64_t g_generic_ws_cap = (int64_t)4 << 30;
 
-// ---- the selection: which kernel runs for (n, p, m, flags, mode) ------------------
+// ---- the selection: which kernel runs for (n, p, m, flags, mode, build) -----------
 // The one statement of the policy: the name functions, the host entries' coverage check and the
 // launch (run) all ask it.  family == kNone: no kernel — a rejected flag combination or a shape
 // (or mode) the family asked for lacks.
 enum Family { kNone, kLane, kSmall, kWave, kGeneric };
+// A family's builds: the exact kernels, the QPGPU_FLAG_FAST restatement, the unit-Hessian kernels of
+// qpgpu_solve_batched_unit.  (An unaligned lane build runs what its aligned twin names.)
+enum Build { kExact, kFast, kUnit };
 struct Pick {
   Family family = kNone;
-  bool fast = false;  // the QPGPU_FLAG_FAST build of the family
+  Build build = kExact;
   const char* name = "";
 };
 
-// The lane family's kernel for (n, m) in `mode`, by build: one row per size class of
-// QPK_LANE_SIZES, NULL where the build has no kernel — the fast and the unit builds restate the
-// plain kernels only.  (An unaligned build runs what its aligned twin names.)
-enum LaneBuild { kLaneExact, kLaneFast, kLaneUnit };
-static const char* lane_name(int n, int m, qpk::Mode mode, LaneBuild build) {
+// Largest shape the generic kernel accepts: n*n and the workspace offsets stay within int64 and a
+// QP's workspace within 2^34 doubles (128 GiB); int32 element indices of the inputs (n*n, n*m).
+// CE offsets (n*p, j*p + i) are computed in int64, so p is not bounded here.
+static bool generic_covers(int n, int m) {
+  return n >= 1 && m >= 0 && (int64_t)n * n < ((int64_t)1 << 31) && (int64_t)n * m < ((int64_t)1 << 31);
+}
+
+// Every kernel's name: one row per size class (n <= nmax, m <= mmax) of the families' lists in
+// qp_common.h, smallest first within a family, and in a row one name per build and mode — NULL
+// where the build has no kernel: the fast and the unit builds restate the plain kernels only, the
+// subgroup and generic families have no fast build, the generic family no unit build, and the wave
+// family's workspace class is the exact build's alone.  A shape runs in its family's first row that
+// holds it; the generic family's one row holds what generic_covers.
+static const char* kernel_name(Family family, Build build, int n, int m, qpk::Mode mode) {
   static const struct {
+    Family family;
     int nmax, mmax;
-    const char* name[3][4];  // [LaneBuild][qpk::Mode]
+    const char* name[3][4];  // [Build][qpk::Mode]
   } rows[] = {
-#define QPK_LANE_NAMES(s)                                                                        \
-  {{"qp_lane<" s ">", "qp_lane_dual<" s ">", "qp_lane_box<" s ">", "qp_lane_box_dual<" s ">"}, \
-   {"qp_lane_fast<" s ">"},                                                                    \
-   {"qp_lane_unit<" s ">"}}
-#define QPK_LANE_ROW(N, M) {N, M, QPK_LANE_NAMES("N=" #N ",M=" #M)},
-      QPK_LANE_SIZES(QPK_LANE_ROW)
+// the exact build's four names (the plain one after `pre`), then the fast and the unit build's
+#define QPK_NAMES(pre, k, s, fast, unit) \
+  {{pre k "<" s ">", k "_dual<" s ">", k "_box<" s ">", k "_box_dual<" s ">"}, {fast}, {unit}}
+#define QPK_NM(N, M) "N=" #N ",M=" #M
+#define QPK_SNM(S, N, M) "S=" #S ",N=" #N ",M=" #M
+#define QPK_LANE_ROW(N, M)                                                                   \
+  {kLane, N, M, QPK_NAMES("", "qp_lane", QPK_NM(N, M), "qp_lane_fast<" QPK_NM(N, M) ">", \
+                          "qp_lane_unit<" QPK_NM(N, M) ">")},
+#define QPK_SMALL_ROW(S, N, M) \
+  {kSmall, N, M, QPK_NAMES("", "qp_small", QPK_SNM(S, N, M), nullptr, "qp_small_unit<" QPK_SNM(S, N, M) ">")},
+#define QPK_WAVE_ROW(S, N, M)                                                                         \
+  {kWave, N, M, QPK_NAMES("", "qp_wave", QPK_SNM(S, N, M), "qp_wave_fast<" QPK_SNM(S, N, M) ">", \
+                          "qp_wave_unit<" QPK_SNM(S, N, M) ">")},
+// (the plain mode's default is the panel path; the other modes always run EXACT, without it)
+#define QPK_WAVE_WS_ROW(S, N, M)                                                                       \
+  {kWave, N, M, QPK_NAMES("qp_panel<MFMA f64 16x16x4> + ", "qp_wave", QPK_SNM(S, N, M) ",global J/R", \
+                          nullptr, nullptr)},
+      QPK_LANE_SIZES(QPK_LANE_ROW) QPK_SMALL_SIZES(QPK_SMALL_ROW) QPK_WAVE_LDS_SIZES(QPK_WAVE_ROW)
+          QPK_WAVE_WS_SIZE(QPK_WAVE_WS_ROW)
+      {kGeneric, INT32_MAX, INT32_MAX, QPK_NAMES("", "qp_generic", "BS=256,global workspace", nullptr, nullptr)},
+#undef QPK_WAVE_WS_ROW
+#undef QPK_WAVE_ROW
+#undef QPK_SMALL_ROW
 #undef QPK_LANE_ROW
-#undef QPK_LANE_NAMES
+#undef QPK_SNM
+#undef QPK_NM
+#undef QPK_NAMES
   };
+  if (family == kGeneric && !generic_covers(n, m)) return nullptr;
   for (const auto& r : rows)
-    if (n <= r.nmax && m <= r.mmax) return r.name[build][mode];
+    if (r.family == family && n <= r.nmax && m <= r.mmax) return r.name[build][mode];
   return nullptr;
 }
 
-static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode) {
+// build: kExact (QPGPU_FLAG_FAST makes it kFast) or kUnit, the selection of qpgpu_solve_batched_unit
+// (DESIGN §3.10): plain mode only, and nothing for QPGPU_FLAG_FAST (there is no fast unit form),
+// QPGPU_FLAG_WRITE_FACTOR (there is no G) and QPGPU_FLAG_FORCE_GENERIC (no unit kernel beyond the
+// wave family's LDS classes: n > 64 and m > 256 have none either).
+static Pick select_kernel(int n, int p, int m, uint32_t flags, qpk::Mode mode, Build build = kExact) {
   if (!flags_valid(flags)) return {};
   // the fast builds restate the plain kernels only: the other modes refuse QPGPU_FLAG_FAST
   if ((flags & QPGPU_FLAG_FAST) && mode != qpk::kPlain) return {};
+  if (build == kUnit && (flags & (QPGPU_FLAG_FAST | QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_FORCE_GENERIC))) return {};
   const uint32_t force = flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP |
                                   QPGPU_FLAG_FORCE_WAVE | QPGPU_FLAG_FORCE_GENERIC);
   // Sizes no launch has (validate): no kernel — except that qpgpu_kernel_name_flags has always
   // answered with a forced family's exact kernel where that family's table admits them.
   const bool sized = n > 0 && p >= 0 && m >= 0;
-  if (!sized && (!force || mode != qpk::kPlain)) return {};
-  const bool fast = (flags & QPGPU_FLAG_FAST) && sized;
+  if (!sized && (!force || mode != qpk::kPlain || build == kUnit)) return {};
+  if ((flags & QPGPU_FLAG_FAST) && sized) build = kFast;
   // A forced family keeps to that family; otherwise lane, subgroup (only where default_small),
   // wave, generic.  With FAST a family's fast build comes first where it covers the shape and its
   // exact kernels otherwise; the subgroup and generic families have none, so FAST | FORCE_GENERIC
   // is the generic kernel and a default_small shape takes the subgroup kernel ahead of the fast
   // wave build.
-  const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
-  const char* s;
-  if (may(QPGPU_FLAG_FORCE_LANE) && (s = lane_name(n, m, mode, fast ? kLaneFast : kLaneExact)))
-    return {kLane, fast, s};
-  if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name(n, m, mode)))
-    return {kSmall, false, s};
-  if (may(QPGPU_FLAG_FORCE_WAVE)) {
-    if (fast && (s = qpk_medium_name_fast(n, m, mode))) return {kWave, true, s};  // LDS variants (n <= 64, m <= 256)
-    if ((s = qpk_medium_name(n, m, mode))) return {kWave, false, s};
+  for (const Family family : {kLane, kSmall, kWave, kGeneric}) {
+    static const uint32_t kForce[] = {0, QPGPU_FLAG_FORCE_LANE, QPGPU_FLAG_FORCE_SUBGROUP, QPGPU_FLAG_FORCE_WAVE,
+                                      QPGPU_FLAG_FORCE_GENERIC};
+    if (force ? force != kForce[family] : (family == kSmall && !default_small(n, m))) continue;
+    if (const char* s = kernel_name(family, build, n, m, mode)) return {family, build, s};
+    if (build != kFast) continue;
+    if (const char* s = kernel_name(family, kExact, n, m, mode)) return {family, kExact, s};
   }
-  if (may(QPGPU_FLAG_FORCE_GENERIC) && (s = qpk_generic_name(n, m, mode)))
-    return {kGeneric, false, s};  // any other shape (n > 256 or m > 1024)
-  return {};
-}
-
-// The selection of qpgpu_solve_batched_unit: the same family order over the families'
-// unit builds — lane, subgroup (only where default_small), the wave kernel's LDS variants — and
-// nothing beyond them: n > 64, m > 256 and QPGPU_FLAG_FORCE_GENERIC have no kernel, and neither do
-// QPGPU_FLAG_FAST (there is no fast unit form) and QPGPU_FLAG_WRITE_FACTOR (there is no G).  A
-// selection of its own, so that select_kernel answers for the existing modes what it always has.
-static Pick select_kernel_unit(int n, int p, int m, uint32_t flags) {
-  if (!flags_valid(flags) || n <= 0 || p < 0 || m < 0) return {};
-  if (flags & (QPGPU_FLAG_FAST | QPGPU_FLAG_WRITE_FACTOR | QPGPU_FLAG_FORCE_GENERIC)) return {};
-  const uint32_t force = flags & (QPGPU_FLAG_FORCE_LANE | QPGPU_FLAG_FORCE_SUBGROUP | QPGPU_FLAG_FORCE_WAVE);
-  const auto may = [&](uint32_t family_flag) { return !force || force == family_flag; };
-  const char* s;
-  if (may(QPGPU_FLAG_FORCE_LANE) && (s = lane_name(n, m, qpk::kPlain, kLaneUnit))) return {kLane, false, s};
-  if ((force ? force == QPGPU_FLAG_FORCE_SUBGROUP : default_small(n, m)) && (s = qpk_small_name_unit(n, m)))
-    return {kSmall, false, s};
-  if (may(QPGPU_FLAG_FORCE_WAVE) && (s = qpk_medium_name_unit(n, m))) return {kWave, false, s};
   return {};
 }
 
 const char* qpgpu_kernel_name_unit(int32_t n, int32_t p, int32_t m, uint32_t flags) {
-  return select_kernel_unit(n, p, m, flags).name;
+  return select_kernel(n, p, m, flags, qpk::kPlain, kUnit).name;
 }
 
 const char* qpgpu_kernel_name_flags(int32_t n, int32_t p, int32_t m, uint32_t flags) {
@@ -338,8 +350,7 @@ static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream, bool un
   if ((!unit && !a.G) || !a.g0 || !a.x || !a.f || !a.status) return QPGPU_ERR_INVALID_ARGUMENT;
   if ((a.p > 0 && (!a.CE || !a.ce0)) || (!a.hi && a.m > 0 && (!a.CI || !a.ci0)))
     return QPGPU_ERR_INVALID_ARGUMENT;
-  const Pick k = unit ? select_kernel_unit(a.n, a.p, a.m, d->flags)
-                      : select_kernel(a.n, a.p, a.m, d->flags, qpk::mode_of(a));
+  const Pick k = select_kernel(a.n, a.p, a.m, d->flags, qpk::mode_of(a), unit ? kUnit : kExact);
   if (k.family == kNone) return QPGPU_ERR_UNSUPPORTED_SHAPE;
   // An empty array (p == 0: CE, ce0; m == 0: CI, ci0) may be passed as NULL, and a torch tensor of
   // no elements has a NULL data_ptr; the box kernels never read CI / ci0.  The wave kernels' l1
@@ -352,46 +363,30 @@ static int run(const qpgpu_problem_desc* d, qpk::QpArgs a, void* stream, bool un
   if (!a.ci0) a.ci0 = a.g0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   std::unique_lock<std::mutex> ws_hold;  // the workspace cache's lock, until the launches are enqueued
+  using Launch = hipError_t (*)(const qpk::QpArgs*, hipStream_t);
   hipError_t e = hipSuccess;
-  if (unit) {
-    // (the lane kernels' staged group is g0, CE and ce0 here: alignment_flags saw a NULL G)
-    switch (k.family) {
-      case kLane:
-        e = (a.flags & qpk::kArgStage16) ? qpk_launch_lane_unit(&a, s) : qpk_launch_lane_unit_u(&a, s);
-        break;
-      case kSmall:
-        e = qpk_launch_small_unit(&a, s);
-        break;
-      case kWave:
-        e = qpk_launch_medium_unit(&a, s);
-        break;
-      default:
-        e = hipErrorInvalidValue;
-        break;
-    }
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return QPGPU_SUCCESS;
-  }
   switch (k.family) {
-    case kLane:
+    case kLane: {
       // The lane kernels stage G, g0, CE and ce0 by 16-byte LDS-DMA: launched only when those arrays
       // are 16-byte aligned, their QPGPU_LANE_UNALIGNED builds (per-lane 8-byte copies) otherwise.
-      if (a.flags & qpk::kArgStage16)
-        e = k.fast ? qpk_launch_lane_fast(&a, s) : qpk_launch_lane(&a, s);
-      else
-        e = k.fast ? qpk_launch_lane_fast_u(&a, s) : qpk_launch_lane_u(&a, s);
+      // (The unit builds' staged group is g0, CE and ce0: alignment_flags saw a NULL G.)
+      static const Launch kLaneLaunch[3][2] = {{qpk_launch_lane_u, qpk_launch_lane},  // [Build][kArgStage16 set]
+                                               {qpk_launch_lane_fast_u, qpk_launch_lane_fast},
+                                               {qpk_launch_lane_unit_u, qpk_launch_lane_unit}};
+      e = kLaneLaunch[k.build][(a.flags & qpk::kArgStage16) != 0](&a, s);
       break;
+    }
     case kSmall:
-      e = qpk_launch_small(&a, s);
+      e = k.build == kUnit ? qpk_launch_small_unit(&a, s) : qpk_launch_small(&a, s);
       break;
     case kWave:
-      if (k.fast) {
-        e = qpk_launch_medium_fast(&a, s);
-      } else {
+      if (k.build == kExact) {
         double* ws = nullptr;
         const int rc = device_workspace(qpk_medium_workspace_bytes(&a), s, &ws, ws_hold);
         if (rc) return rc;
         e = qpk_launch_medium(&a, s, ws);
+      } else {
+        e = k.build == kUnit ? qpk_launch_medium_unit(&a, s) : qpk_launch_medium_fast(&a, s);
       }
       break;
     case kGeneric:

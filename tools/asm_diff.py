@@ -34,6 +34,9 @@ def split(lines):
                 name = None
             continue
         rest.append(ln)
+    if name is not None:  # a device variable's label after the last function: no .Lfunc_end follows
+        order.pop()
+        rest += [name + ":"] + cur
     return ker, rest, order
 
 
